@@ -19,7 +19,7 @@ if [ -n "$TESTS" ]; then
     tests/test_gpu_fullsize.py tests/test_shard_search_gpu.py -k "$TESTS" > "$out/tests.log" 2>&1
   rc=$?; tail -2 "$out/tests.log"; [ $rc -eq 0 ] || exit $rc
 fi
-B="--no-cpu-baseline --no-config2 --no-config0 --no-msmarco-search"
+B="--full --no-cpu-baseline --no-config2 --no-config0 --no-msmarco-search"
 vars=("$@"); rev=(); for ((i=${#vars[@]}-1; i>=0; i--)); do rev+=("${vars[$i]}"); done
 n=0
 for v in "${vars[@]}" "${rev[@]}"; do

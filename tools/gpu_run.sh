@@ -16,7 +16,7 @@ if [ -z "$NO_TESTS" ]; then
   if [ $rc -ne 0 ]; then echo "smoke rc=$rc: stopping"; exit $rc; fi
 fi
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 900 python bench.py ${BENCH_ARGS:---steps 20 --warmup 5} > "$out/bench.json" 2> "$out/bench.err"
+  timeout -k 10 900 python bench.py ${BENCH_ARGS:---full --steps 20 --warmup 5} > "$out/bench.json" 2> "$out/bench.err"
   rc=$?; tail -c 600 "$out/bench.json"; tail -3 "$out/bench.err"
   exit $rc
 fi

@@ -3,7 +3,7 @@
     python tools/prof_check.py TRACE_CSV[.gz] BENCH_JSON OUT_JSON [UNTRACED_BENCH_JSON]
 
 TRACE_CSV is the `--kernel-trace` output of a `rocprofv3 ... -- python3
-bench.py` run and BENCH_JSON the line that same run printed.  Every roofline
+bench.py --full` run and BENCH_JSON the line that same run printed.  Every roofline
 object in the line that names its kernel symbol and launch shape
 (`symbol`, `grid_threads`, see bench.py attach_traffic) is matched with the
 dispatches of that symbol and shape in the trace; the output lists, per

@@ -9,7 +9,7 @@ set -o pipefail
 OUT=$1; shift
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="bench.py --steps 20 --warmup 5"
+B="bench.py --full --steps 20 --warmup 5"
 for st in "$@"; do
   case $st in
     bench) timeout -k 10 900 python3 $B > $OUT/bench.json 2> $OUT/bench.err || exit 1 ;;

@@ -7,7 +7,7 @@ if [ -n "$TESTS" ]; then
     tests/test_gpu_fullsize.py tests/test_shard_search_gpu.py -k "$TESTS" > $out/tests.log 2>&1
   rc=$?; tail -2 $out/tests.log; [ $rc -eq 0 ] || exit $rc
 fi
-B="--steps 5 --warmup 2 --no-cpu-baseline --no-config2 --no-config0 --no-msmarco-search --no-single"
+B="--full --steps 5 --warmup 2 --no-cpu-baseline --no-config2 --no-config0 --no-msmarco-search --no-single"
 for a in "$@"; do
   timeout -k 10 300 python -u bench.py $B $a > $out/b.json 2>> $out/err.log || exit 1
   python tools/ab_summary.py bigann "$a" $out/b.json | tee -a $out/summary.log

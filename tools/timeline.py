@@ -1,4 +1,4 @@
-"""GPU timeline of a serving run (PM_TIMELINE=<file> python bench.py ...:
+"""GPU timeline of a serving run (PM_TIMELINE=<file> python bench.py --full ...:
 every timed launch of the kernel-timing pass as kernel,start_us,end_us,ctx).
 
 python tools/timeline.py FILE
