@@ -66,7 +66,7 @@ def build(force: bool = False, verbose: bool = True) -> Path:
 
 
 def build_variant(name: str, defines: list[str]) -> Path:
-    """An experiment build (e.g. -DPM_PUBLISH=0) at build/libpacmann_<name>.so,
+    """An experiment build (e.g. -DPM_ROT_HPL=4) at build/libpacmann_<name>.so,
     loaded instead of the default with PM_LIB=<path>."""
     out = ROOT / "build" / f"libpacmann_{name}.so"
     out.parent.mkdir(exist_ok=True)

@@ -43,10 +43,6 @@ __device__ __forceinline__ uint32_t bs_ax(uint32_t a, uint32_t b, uint32_t c) {
 // circuit with every AND that feeds one XOR fused into it ((a & b) ^ c) and
 // XOR pairs merged into three-input XORs: 85 VALU instead of 113 gates, the
 // round constant k (wave-uniform) riding in the output XORs.
-#ifndef PM_BS_KMODE
-#define PM_BS_KMODE 0   // round constants: 0 = planes made on the SALU from the byte (s_bfe), 1 = planes read
-                        // from LDS (precomputed per workgroup), 2 = none (timing experiment only: wrong output)
-#endif
 // The constant byte as the S-box consumes it: plane b of q[b]'s constant is bit b
 // of bs_kk(k) (q[3] = tc14 ^ q[4] needs k3 ^ k4, q[6] = q[4] ^ tc16 needs k6 ^ k4).
 __device__ __host__ __forceinline__ uint32_t bs_kk(uint32_t k) {
@@ -56,7 +52,7 @@ struct BsK { uint32_t v[8]; };
 __device__ __forceinline__ BsK bs_kplanes(uint32_t kk) {
   BsK r;
 #pragma unroll
-  for (int b = 0; b < 8; ++b) r.v[b] = PM_BS_KMODE == 2 ? 0u : bs_kp(kk, b);
+  for (int b = 0; b < 8; ++b) r.v[b] = bs_kp(kk, b);   // made on the SALU from the wave-uniform byte (s_bfe)
   return r;
 }
 __device__ __forceinline__ void bs_sbox(const uint32_t (&p)[8], uint32_t (&q)[8], const BsK& K) {
@@ -117,15 +113,11 @@ __device__ __forceinline__ void bs_mc_row(const uint32_t (&ai)[8], const uint32_
 // One full round on the state (S-box with the round's folded key, ShiftRows,
 // MixColumns).  kw: the round's 16 constant bytes (k'_r ^ 0x63) as 4 words,
 // byte p = 4 col + row, wave-uniform.
-__device__ __forceinline__ BsK bs_kload(const uint32_t* kpl) {   // 8 planes from LDS (broadcast reads)
-  const uint4 a = *reinterpret_cast<const uint4*>(kpl), b = *reinterpret_cast<const uint4*>(kpl + 4);
-  return BsK{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
-}
-__device__ __forceinline__ void bs_round(uint32_t (&s)[16][8], const uint32_t (&kw)[4], const uint32_t* kpl) {
+__device__ __forceinline__ void bs_round(uint32_t (&s)[16][8], const uint32_t (&kw)[4]) {
   uint32_t t[16][8];
 #pragma unroll
   for (int p = 0; p < 16; ++p)
-    bs_sbox(s[p], t[p], PM_BS_KMODE == 1 ? bs_kload(kpl + 8 * p) : bs_kplanes((kw[p >> 2] >> (8 * (p & 3))) & 0xffu));
+    bs_sbox(s[p], t[p], bs_kplanes((kw[p >> 2] >> (8 * (p & 3))) & 0xffu));
   // column c after ShiftRows: row r from byte 4 ((c + r) & 3) + r
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
@@ -222,16 +214,9 @@ __device__ __forceinline__ void bs_setup_a(const uint32_t* te0, const uint32_t* 
     wv[t - 64][0] = u[0]; wv[t - 64][1] = u[1]; wv[t - 64][2] = u[2]; wv[t - 64][3] = u[3];
   }
 }
-// wp[8 p + b] = the plane (byte p, bit b) of W(j) = wv[j] ^ wv[0];
-// PM_BS_KMODE 1: kpl[128 (r-3) + 8 p + b] = plane b of round r's constant byte p
-constexpr int kBsKplWords = PM_BS_KMODE == 1 ? 7 * 128 : 1;
-__device__ __forceinline__ void bs_setup_b(const uint32_t (*wv)[4], uint32_t* wp, const uint32_t* kx, uint32_t* kpl) {
+// wp[8 p + b] = the plane (byte p, bit b) of W(j) = wv[j] ^ wv[0]
+__device__ __forceinline__ void bs_setup_b(const uint32_t (*wv)[4], uint32_t* wp) {
   const uint32_t t = threadIdx.x;
-  if (PM_BS_KMODE == 1)
-    for (uint32_t i = t; i < 7 * 128; i += blockDim.x) {
-      const uint32_t r = i >> 7, p = (i >> 3) & 15, b = i & 7;
-      kpl[i] = bs_kp((kx[4 * r + (p >> 2)] >> (8 * (p & 3))) & 0xffu, b);
-    }
   if (t < 128) {
     const uint32_t p = t >> 3, b = t & 7, sh = 8 * (p & 3) + b, w = p >> 2;
     const uint32_t z = (wv[0][w] >> sh) & 1u;
@@ -245,7 +230,7 @@ __device__ __forceinline__ void bs_setup_b(const uint32_t (*wv)[4], uint32_t* wp
 // 16 PRF-output planes (bits 0..15 of PRF(32 m + j, x) ^ ...): lo16 of the PRF
 // for the lane's 32 tags at chunk x.  kx / wp from the setup (LDS).
 __device__ __forceinline__ void bs_prf16(const uint32_t* te0, const uint32_t* __restrict__ rk, const uint32_t* kx,
-                                         const uint32_t* wp, const uint32_t* kpl, uint32_t m, uint32_t x,
+                                         const uint32_t* wp, uint32_t m, uint32_t x,
                                          uint32_t (&o)[16]) {
   // keep the W planes' LDS reads inside the caller's loop (hoisted, they would
   // pin 128 VGPRs for the whole kernel)
@@ -265,15 +250,13 @@ __device__ __forceinline__ void bs_prf16(const uint32_t* te0, const uint32_t* __
     uint32_t kw[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) kw[i] = __builtin_amdgcn_readfirstlane(kx[4 * r + i]);
-    bs_round(s, kw, kpl + 128 * r);
+    bs_round(s, kw);
   }
   // round 9: the S-boxes of columns 0 and 1 after ShiftRows, MixColumns rows 0 / 1
   uint32_t kw9[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) kw9[i] = __builtin_amdgcn_readfirstlane(kx[24 + i]);
-  auto kb = [&](int p) {
-    return PM_BS_KMODE == 1 ? bs_kload(kpl + 6 * 128 + 8 * p) : bs_kplanes((kw9[p >> 2] >> (8 * (p & 3))) & 0xffu);
-  };
+  auto kb = [&](int p) { return bs_kplanes((kw9[p >> 2] >> (8 * (p & 3))) & 0xffu); };
   uint32_t a0[8], a1[8], a2[8], a3[8], u00[8], u11[8];
   bs_sbox(s[0], a0, kb(0)); bs_sbox(s[5], a1, kb(5)); bs_sbox(s[10], a2, kb(10)); bs_sbox(s[15], a3, kb(15));
   bs_mc_row(a0, a1, a2, a3, u00);   // column 0 row 0

@@ -3,8 +3,6 @@
 // graphann beam search over PIRGraphInfo, and the extern "C" boundary of
 // include/pacmann.h.
 #include <dlfcn.h>
-#include <pthread.h>
-#include <sched.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types only: the functions are resolved at run time (rccl_api)
 
@@ -189,10 +187,10 @@ struct pm_ctx {
   uint64_t sample_ctr = 0;
   bool no_fuse = false;      // PM_NO_FUSE=1: the three step kernels even when k_step fits
   bool no_split = false;     // PM_NO_SPLIT=1: k_answer gathers wide sets itself (no k_gather)
-  bool no_guess = false;
-  bool verify_rows = false;
-  bool debug_cache = false;
-  bool log_steps = false;    // PM_LOG_STEPS=1: one stderr line per sub-query per step  // PM_DEBUG_CACHE=1: check cached answers against the slot's first answer  // PM_VERIFY_ROWS=1: re-read each step's results after the stream drains     // PM_NO_GUESS=1: k_step answers do not start before their resolution
+  bool no_guess = false;     // PM_NO_GUESS=1: k_step answers do not start before their resolution
+  bool verify_rows = false;  // PM_VERIFY_ROWS=1: re-read each step's results after the stream drains
+  bool debug_cache = false;  // PM_DEBUG_CACHE=1: check cached answers against the slot's first answer
+  bool log_steps = false;    // PM_LOG_STEPS=1: one stderr line per sub-query per step
   bool debug_sync = false;   // PM_DEBUG_SYNC=1: synchronise after every launch (fault triage)
   // Maintenance: the replacement rows (HBM copies, independent of the PRF
   // tables and the fold) run on a side stream beside k_prep_offsets
@@ -2723,13 +2721,7 @@ static void group_stage_session(StepGroup& G, uint32_t s) {
 // search + resolution (k_match_resolve_s where the shapes hold), the split
 // gather for wide sets, the answer; the completion event unless the records
 // go to a combine.  (group_step; the device loop's steps, run_batched_dev.)
-// ans_st (device loop, PM_ANSWER_STREAM): the answer runs on that stream, one
-// shared by every team, between two events (after this step's match + resolve,
-// before the team's next kernel): the teams' answers, which all read HBM, run
-// one at a time at the full gather rate while the teams' latency-bound chain
-// kernels run beside them.
-static int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uint32_t nreal, double ans_bytes,
-                             hipStream_t ans_st = nullptr, hipEvent_t* ans_ev = nullptr) {
+static int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uint32_t nreal, double ans_bytes) {
   pm_ctx* c = G.c;
   hipStream_t st = c->stream;
   const uint32_t nsub = S.nsub, np = S.np;
@@ -2793,15 +2785,7 @@ static int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uin
     S.stamps = G.stamps.as<uint64_t>();
   }
 #endif
-  if (ans_st) {
-    HIPCHK(hipEventRecord(ans_ev[0], st));
-    HIPCHK(hipStreamWaitEvent(ans_st, ans_ev[0], 0));
-    c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { pmk::step_answer(ans_st, S, G.maxSS, ev); }, 2);
-    HIPCHK(hipEventRecord(ans_ev[1], ans_st));
-    HIPCHK(hipStreamWaitEvent(st, ans_ev[1], 0));
-  } else {
-    c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { pmk::step_answer(st, S, G.maxSS, ev); }, 2);
-  }
+  c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { pmk::step_answer(st, S, G.maxSS, ev); }, 2);
   if (!G.comb) G.seq = c->record_done(st);   // sharded: group_exchange publishes the records
   HIPCHK(hipGetLastError());
 #ifdef PM_ANSWER_STAMPS
@@ -3728,68 +3712,22 @@ struct PoolTeam {
 // whose in-order packets serialise the teams' kernels.  The teams get streams
 // of their own instead, created back to back once per device (so they take
 // distinct hardware queues), swapped into the team's context for the loop
-// (PM_TEAM_STREAMS=0: the context streams).
-// PM_PREP_CUS=X (the device loop): the maintenance runs on a stream limited to
-// X CUs and the teams on the other ones, so one team's maintenance (the fold
-// and the AES tables: LDS-bound, a workgroup filling its CU) runs beside the
-// other teams' queries (HBM-bound answers) instead of taking the whole GPU in
-// turn.  Meant with the teams' maintenance windows staggered (bench.py
-// --stagger-teams).  0: off.  PM_CU_MAP: how mask bits map to XCDs (0: 32
-// consecutive bits per XCD, 1: bit i on XCD i % 8); X / 8 CUs are taken from
-// every XCD either way (default 1).
-static int prep_cus() {
-  static const int v = [] { const char* e = getenv("PM_PREP_CUS"); return e ? std::max(0, atoi(e)) : 0; }();
-  return v;
-}
-static std::vector<uint32_t> cu_mask(int dev, uint32_t n, bool complement) {
-  // (profiles/r05/cumask_bench.txt: one 32-bit mask word spans all 8 XCDs, i.e. bit i is on XCD i % 8)
-  static const int map = [] { const char* e = getenv("PM_CU_MAP"); return e ? atoi(e) : 1; }();
-  int ncu = 256;
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  const uint32_t per = (uint32_t)ncu / 8, take = std::min(per, n / 8);
-  std::vector<uint32_t> m(((uint32_t)ncu + 31) / 32, 0);
-  for (uint32_t i = 0; i < (uint32_t)ncu; ++i) {
-    const uint32_t j = map == 1 ? i / 8 : i % per;   // index of CU i inside its XCD
-    const bool on = (j < take) != complement;
-    if (on) m[i / 32] |= 1u << (i % 32);
-  }
-  return m;
-}
-static hipStream_t masked_stream(int dev, uint32_t n, bool complement) {
-  std::vector<uint32_t> m = cu_mask(dev, n, complement);
-  hipStream_t st = nullptr;
-  if (hipExtStreamCreateWithCUMask(&st, (uint32_t)m.size(), m.data()) != hipSuccess) return nullptr;
-  return st;
-}
+// (the context streams where none can be created).
 static hipStream_t team_stream(int dev, uint32_t t) {
   static std::mutex mu;
   static std::vector<hipStream_t> pool[64];
-  static const int on = [] { const char* e = getenv("PM_TEAM_STREAMS"); return e ? atoi(e) : 1; }();
-  // PM_TEAM_CUS=1: the teams on the complement of the maintenance's CUs
-  // (a static split; default: the teams keep every CU)
-  static const int split = [] { const char* e = getenv("PM_TEAM_CUS"); return e ? atoi(e) : 0; }();
-  if ((!on && !(prep_cus() && split)) || dev < 0 || dev >= 64) return nullptr;
+  if (dev < 0 || dev >= 64) return nullptr;
   std::lock_guard<std::mutex> lk(mu);
   std::vector<hipStream_t>& v = pool[dev];
   if (v.empty()) {
     for (int i = 0; i < 8; ++i) {
       hipStream_t st = nullptr;
-      if (prep_cus() && split) st = masked_stream(dev, (uint32_t)prep_cus(), true);
-      else if (on == 2) st = masked_stream(dev, 1u << 16, false);   // every CU: a CU-masked stream's own queue
-      else if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) st = nullptr;
+      if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) st = nullptr;
       if (!st) break;
       v.push_back(st);
     }
   }
   return v.empty() ? nullptr : v[t % v.size()];
-}
-static hipStream_t prep_stream(int dev) {
-  static std::mutex mu;
-  static hipStream_t st[64] = {};
-  if (!prep_cus() || dev < 0 || dev >= 64) return nullptr;
-  std::lock_guard<std::mutex> lk(mu);
-  if (!st[dev]) st[dev] = masked_stream(dev, (uint32_t)prep_cus(), false);
-  return st[dev];
 }
 struct StreamSwap {   // a team context's stream replaced for the loop's duration (restored drained)
   pm_ctx* c = nullptr;
@@ -3824,14 +3762,6 @@ static int run_batched_pool(pm_graph** gs, uint32_t S, const float* queries, uin
   // Q.  The maintenance kernels fill the GPU, so teams' maintenances run one
   // after another either way; merged, the teams also resume together instead
   // of finishing the timed work one after another with the GPU partly idle.
-  // PM_PREP_MERGE=0 (or the former name PM_PREP_WAIT_MS=0): each team's
-  // maintenance alone, when it reaches it; otherwise merged as above.  (Not a
-  // time: a team waits for the others' query Q only, never longer.)
-  static const double prep_wait = [] {
-    const char* e = getenv("PM_PREP_MERGE");
-    if (!e) e = getenv("PM_PREP_WAIT_MS");
-    return e ? atof(e) : 1.0;
-  }();
   struct Release {
     std::vector<std::unique_ptr<PoolTeam>>& t;
     ~Release() { for (auto& x : t) team_release(x->gs, x->S); }
@@ -3871,9 +3801,8 @@ static int run_batched_pool(pm_graph** gs, uint32_t S, const float* queries, uin
   // a session of the open phase: worker w's own lane first (sessions i = w mod
   // T: the same worker, hence core, serves a session every round and finds its
   // search state and prefetched rows in cache), then the other lanes' leftovers
-  static const int steal = [] { const char* e = getenv("PM_POOL_STEAL"); return e ? atoi(e) : 1; }();
   auto claim = [&](PoolTeam& t, uint32_t w) -> uint32_t {
-    for (uint32_t j = 0; j < (steal ? T : 1u); ++j) {
+    for (uint32_t j = 0; j < T; ++j) {
       const uint32_t l = (w + j) % T;
       if (l >= t.S) continue;
       if (t.lane[l].load(std::memory_order_relaxed) * T + l >= t.S) continue;
@@ -3946,7 +3875,7 @@ static int run_batched_pool(pm_graph** gs, uint32_t S, const float* queries, uin
     const double t0 = tr.now();
     bool any = false;
     for (char c : t.need_prep) any |= c != 0;
-    if (any && prep_wait > 0) {   // with the other teams' (above)
+    if (any) {   // with the other teams' (above)
       t.prep_since = Clock::now();
       t.state.store(kTeamPrep, std::memory_order_release);
       return 0;
@@ -3962,31 +3891,8 @@ static int run_batched_pool(pm_graph** gs, uint32_t S, const float* queries, uin
   };
   std::vector<int64_t> steps_buf((size_t)T * std::max(k, 1));
   const int dev = gs[0]->ctx->device;
-  // PM_PIN_WORKERS=1: worker w runs on the w-th CPU of the process's affinity
-  // mask, so the sessions of its lane keep their state in one core's caches
-  static const int pin = [] { const char* e = getenv("PM_PIN_WORKERS"); return e ? atoi(e) : 0; }();
-  std::vector<int> cpus;
-  if (pin) {
-    cpu_set_t cs;
-    if (sched_getaffinity(0, sizeof cs, &cs) == 0)
-      for (int c = 0; c < CPU_SETSIZE; ++c)
-        if (CPU_ISSET(c, &cs)) cpus.push_back(c);
-    if (cpus.size() < T) cpus.clear();
-  }
   auto worker = [&](uint32_t w) {
     TeamTrace::tl_worker = w;
-    cpu_set_t old_set;
-    const bool pinned = !cpus.empty() && pthread_getaffinity_np(pthread_self(), sizeof old_set, &old_set) == 0;
-    if (pinned) {
-      cpu_set_t one;
-      CPU_ZERO(&one);
-      CPU_SET(cpus[w], &one);
-      (void)pthread_setaffinity_np(pthread_self(), sizeof one, &one);
-    }
-    struct Unpin {   // worker 0 is the caller's thread: its affinity is restored
-      bool on; cpu_set_t set;
-      ~Unpin() { if (on) (void)pthread_setaffinity_np(pthread_self(), sizeof set, &set); }
-    } unpin{pinned, old_set};
     if (hipSetDevice(dev) != hipSuccess) { set_err(PM_EHIP, 0); return; }
     int64_t* stp = &steps_buf[(size_t)w * std::max(k, 1)];
     uint32_t idle = 0;
@@ -4194,8 +4100,6 @@ struct DrlTeam {
       step_bytes, step_real, stamps;
   DrlArgs A{};
   hipEvent_t ev_end = nullptr;
-  hipStream_t ans_st = nullptr;                  // the shared answer stream (null: the team's own)
-  hipEvent_t ans_ev[2] = {};
   HostBuf prep_stage, parts_stage;               // pinned stages of the asynchronous maintenance (run_batched_dev)
   hipEvent_t prep_stage_ev = nullptr, parts_stage_ev = nullptr;
   DevBuf prep_buf;
@@ -4204,7 +4108,7 @@ struct DrlTeam {
   std::vector<char> need;
   std::vector<double> mt;
   ~DrlTeam() {
-    for (hipEvent_t e : {ev_end, prep_stage_ev, parts_stage_ev, ans_ev[0], ans_ev[1]})
+    for (hipEvent_t e : {ev_end, prep_stage_ev, parts_stage_ev})
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -4356,7 +4260,7 @@ static int drl_step(DrlTeam& T, const DrlShape& sh) {
   // bytes: every sub-query answered (patched with the round's exact count in timing runs)
   double ans_bytes = 0;
   for (uint32_t li = 0; li < G.Pl; ++li) ans_bytes += answer_bytes(e0->parts[G.lp[li]].d, G.E) * sh.qn * T.S;
-  CHK(group_step_launch(G, S, sh.qn, T.nsub, ans_bytes, T.ans_st, T.ans_ev));
+  CHK(group_step_launch(G, S, sh.qn, T.nsub, ans_bytes));
   for (size_t i = before; i < c->launches.size(); ++i)
     if (c->launches[i].name == "answer" || c->launches[i].name == "match_resolve" || c->launches[i].name == "hint_match")
       T.tl.emplace_back(i, T.seq - 1);   // the step the last BEGIN / MID round built (drl_round advanced seq)
@@ -4479,34 +4383,6 @@ static int run_batched_dev_body(pm_graph** gs, uint32_t S, const float* queries,
     CHK(drl_team_init(*teams.back(), gs + s0, s1 - s0, s0, queries, q, k, step, parallel, sh));
     swaps[g].swap_in(teams.back()->G.c, team_stream(teams.back()->G.c->device, g));
   }
-  static const int ans_stream = [] { const char* e = getenv("PM_ANSWER_STREAM"); return e ? atoi(e) : 0; }();
-  if (ans_stream == 1 && NG > 1) {   // the last stream of the pool (created first-to-last: its own hardware queue)
-    hipStream_t as = team_stream(teams[0]->G.c->device, 7);
-    for (auto& t : teams) {
-      t->ans_st = as;
-      for (auto& e : t->ans_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-  } else if (ans_stream >= 2) {
-    // PM_ANSWER_STREAM=2: each team's answers on a stream of its own limited to
-    // all CUs but PM_ANSWER_RESERVE_CUS (default 16, 2 per XCD), so the
-    // chain kernels (match + resolve, the team round) always find free slots
-    static const int reserve = [] { const char* e = getenv("PM_ANSWER_RESERVE_CUS"); return e ? atoi(e) : 16; }();
-    static std::vector<hipStream_t> ast[64];
-    const int dev = teams[0]->G.c->device;
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (dev >= 0 && dev < 64) {
-      while (ast[dev].size() < teams.size()) {
-        hipStream_t st = masked_stream(dev, (uint32_t)std::max(8, ncu - reserve), false);
-        if (!st) break;
-        ast[dev].push_back(st);
-      }
-      for (size_t i = 0; i < teams.size() && i < ast[dev].size(); ++i) {
-        teams[i]->ans_st = ast[dev][i];
-        for (auto& e : teams[i]->ans_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      }
-    }
-  }
   // Maintenance launch sets, timed by events around them on the leader's stream
   struct PrepSet { hipEvent_t a = nullptr, b = nullptr; std::vector<std::pair<DrlTeam*, uint32_t>> members; };
   std::vector<PrepSet> sets;
@@ -4536,12 +4412,10 @@ static int run_batched_dev_body(pm_graph** gs, uint32_t S, const float* queries,
     // stream after every involved team's query; nothing on the host waits for
     // it (the other teams keep running what is queued), and the involved
     // teams' next rounds wait for it on the device
-    // (PM_PREP_CUS: on the maintenance stream's CUs, beside the other teams)
     DrlTeam* L = involved[0];
-    hipStream_t const pst = prep_stream(L->G.c->device);
-    hipStream_t sl = pst ? pst : L->G.c->stream;
+    hipStream_t const sl = L->G.c->stream;
     for (DrlTeam* t : involved)
-      if (t != L || pst) {
+      if (t != L) {
         HIPCHK(hipEventRecord(t->ev_end, t->G.c->stream));
         HIPCHK(hipStreamWaitEvent(sl, t->ev_end, 0));
       }
@@ -4550,11 +4424,6 @@ static int run_batched_dev_body(pm_graph** gs, uint32_t S, const float* queries,
     HIPCHK(hipEventCreate(&ps.a));
     HIPCHK(hipEventCreate(&ps.b));
     HIPCHK(hipEventRecord(ps.a, sl));
-    struct OnStream {   // the leader's context launches on sl for the set
-      pm_ctx* c; hipStream_t old;
-      OnStream(pm_ctx* cc, hipStream_t st) : c(cc), old(cc->stream) { c->stream = st; }
-      ~OnStream() { c->stream = old; }
-    } on_sl(L->G.c, sl);
     CHK(prep_clients(L->G.c, L->prep_buf, L->G.lp, who, nullptr, &L->prep_stage, &L->prep_stage_ev));
     for (DrlTeam* t : involved) {   // the new keys into the team's parts; the emptied localCache indexes
       CHK(group_upload_parts_async(t->G, sl, t->parts_stage, t->parts_stage_ev));
@@ -4566,10 +4435,8 @@ static int run_batched_dev_body(pm_graph** gs, uint32_t S, const float* queries,
     }
     HIPCHK(hipEventRecord(ps.b, sl));
     for (DrlTeam* t : involved)
-      if (t != L || pst) HIPCHK(hipStreamWaitEvent(t == L ? on_sl.old : t->G.c->stream, ps.b, 0));
+      if (t != L) HIPCHK(hipStreamWaitEvent(t->G.c->stream, ps.b, 0));
   }
-  for (auto& t : teams)
-    if (t->ans_st) HIPCHK(hipStreamSynchronize(t->ans_st));
   for (auto& t : teams) CHK(drl_team_finish(*t, q, k, answers));
   for (PrepSet& ps : sets) {   // each triggered client's maintenance time: its launch set's span on the GPU
     float ms = 0;

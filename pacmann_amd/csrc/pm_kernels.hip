@@ -43,15 +43,11 @@ constexpr int kOffsBlock = 1024;   // 64 KiB of replicated table per workgroup: 
 // them the kernel is only 2 % faster).  1,024-thread workgroups share one 64 KiB
 // table copy (the LDS init is 4 B per PRF, not 16) and keep 16 waves per CU
 // for the lookups' latency: 0.370 -> 0.335 ms at SIFT1M shape.
-#ifndef PM_OFFS_PAIR
-#define PM_OFFS_PAIR 0   // k_prep_offsets: two chunks' PRFs per iteration (61 VGPRs at 8 waves: 56.5 vs 54.2 ms
-                         // per 288-client launch, profiles/r05/ab/aes_chunk_pairs.log)
-#endif
 #ifndef PM_OFFS_TILES
 #define PM_OFFS_TILES 1   // 8-chunk tiles per workgroup sharing one 64 KiB table fill (2 and 4 measured no faster: 244 / 268 vs 240 us per client alone)
 #endif
 constexpr int kOffsTiles = PM_OFFS_TILES;
-__global__ void __launch_bounds__(kOffsBlock, PM_OFFS_PAIR ? 8 : 1) k_prep_offsets(const PmPart* __restrict__ parts) {
+__global__ void __launch_bounds__(kOffsBlock, 1) k_prep_offsets(const PmPart* __restrict__ parts) {
   __shared__ uint32_t te[kTeLdsWords];
   __shared__ R1Uniform r1u[kOffsTiles][kOffsChunksPerBlock];
   const PmPart& P = parts[blockIdx.z];
@@ -90,26 +86,8 @@ __global__ void __launch_bounds__(kOffsBlock, PM_OFFS_PAIR ? 8 : 1) k_prep_offse
       tile[c - c0] = v;
       if (h < P.PH) P.cur[cur_index(P.PH, P.curk, c, h)] = v;   // hint search (tags start at h)
     };
-#if PM_OFFS_PAIR
-    // two chunks' PRFs as independent chains side by side (twice the lookups in
-    // flight per lane for the LDS latency)
-    for (uint32_t c = c0; c < c1; c += 2) {
-      const uint32_t cB = min(c + 1, c1 - 1);
-      uint32_t pa, pb;
-      if (r2) {
-        pa = prf_lo16_r2(A, P.rk, r1u[tl][c - c0].u0, r1v, r2k, c);
-        pb = prf_lo16_r2(A, P.rk, r1u[tl][cB - c0].u0, r1v, r2k, cB);
-      } else {
-        pa = prf_lo16_split(A, P.rk, r1u[tl][c - c0], r1v, c);
-        pb = prf_lo16_split(A, P.rk, r1u[tl][cB - c0], r1v, cB);
-      }
-      put(c, pa);
-      if (cB != c) put(cB, pb);
-    }
-#else
     for (uint32_t c = c0; c < c1; ++c)
       put(c, r2 ? prf_lo16_r2(A, P.rk, r1u[tl][c - c0].u0, r1v, r2k, c) : prf_lo16_split(A, P.rk, r1u[tl][c - c0], r1v, c));
-#endif
     uint4 t4;   // tag-major tile (set expansion): one 16-B store
     t4.x = tile[0] | ((uint32_t)tile[1] << 16); t4.y = tile[2] | ((uint32_t)tile[3] << 16);
     t4.z = tile[4] | ((uint32_t)tile[5] << 16); t4.w = tile[6] | ((uint32_t)tile[7] << 16);
@@ -140,7 +118,6 @@ __global__ void __launch_bounds__(kBsThreads, PM_BS_WAVES) k_prep_offsets_bs(con
   __shared__ uint32_t bs_wv[32][4];
   __shared__ __attribute__((aligned(16))) uint32_t bs_wp[128];
   __shared__ __attribute__((aligned(16))) uint32_t bs_stash[16 * kBsThreads];
-  __shared__ __attribute__((aligned(16))) uint32_t bs_kpl[kBsKplWords];
   const PmPart& P = parts[blockIdx.y];
   const uint32_t H = P.H, SS = P.SS, PH = P.PH;
   const uint32_t nm = (H + 31) / 32, ng = (SS + 7) / 8;
@@ -149,7 +126,7 @@ __global__ void __launch_bounds__(kBsThreads, PM_BS_WAVES) k_prep_offsets_bs(con
   __syncthreads();
   bs_setup_a(bs_te0, P.rk, bs_kx, bs_wv);
   __syncthreads();
-  bs_setup_b(bs_wv, bs_wp, bs_kx, bs_kpl);
+  bs_setup_b(bs_wv, bs_wp);
   __syncthreads();
   const uint32_t task = blockIdx.x * kBsThreads + threadIdx.x;
   if (task >= nm * ng) return;
@@ -167,7 +144,7 @@ __global__ void __launch_bounds__(kBsThreads, PM_BS_WAVES) k_prep_offsets_bs(con
     uint32_t T[32];
     if (c < SS) {   // SetSize is a multiple of 4: a pair is whole
       uint32_t o[16];
-      bs_prf16(bs_te0, P.rk, bs_kx, bs_wp, bs_kpl, m, cc, o);
+      bs_prf16(bs_te0, P.rk, bs_kx, bs_wp, m, cc, o);
       // backup hints whose own chunk is cc (pir.go:332-334): kSkip (all 16 bits set)
       const int lo = (int)(PH + cc * Qpc) - (int)h0, hi = lo + (int)Qpc;
       const uint32_t own = lowmask(hi) & ~lowmask(lo);
@@ -418,9 +395,6 @@ __device__ __forceinline__ void wait_vmcnt(uint32_t n) {
   }
 }
 
-#ifndef PM_FOLD_FLIP
-#define PM_FOLD_FLIP 1
-#endif
 // G = 16-B staging loads per thread per chunk; NB LDS buffers; D chunks folded
 // between two workgroup barriers
 template <int SW, int G, int NB, int D = 1>
@@ -501,14 +475,11 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_pipe(const PmPart* _
   // random rows pile up ~4.4-deep on 8 slots.  Odd lanes read the row's halves
   // in the other order (their accumulator holds words 2-3 first): each group's
   // 8 even and 8 odd lanes then fall on disjoint slot sets (~3.1-deep).
-  const uint32_t fl = (SW == 4 && PM_FOLD_FLIP) ? ((tid & 1u) << 1) : 0u;
-#ifndef PM_FOLD_ABL
-#define PM_FOLD_ABL 0   // diagnostic builds: 1 = no LDS compute, 2 = no staging in the loop
-#endif
+  const uint32_t fl = SW == 4 ? ((tid & 1u) << 1) : 0u;
   for (uint32_t c0 = 0; c0 < SS; c0 += D) {
 #pragma unroll
     for (int j = 0; j < D; ++j)
-      if (PM_FOLD_ABL != 2 && c0 + NB - D + j < SS) stage(c0 + NB - D + j, (c0 + NB - D + j) % NB);
+      if (c0 + NB - D + j < SS) stage(c0 + NB - D + j, (c0 + NB - D + j) % NB);
 #pragma unroll
     for (int j = 0; j < D; ++j) {
     const uint32_t c = c0 + j;
@@ -516,7 +487,7 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_pipe(const PmPart* _
     const uint64_t* L = fold_lds + (c % NB) * BUFW;
     const uint16_t* T = reinterpret_cast<const uint16_t*>(L + TABW);
 #pragma unroll
-    for (int k = 0; k < (PM_FOLD_ABL == 1 ? 0 : kFoldHPT); ++k) {
+    for (int k = 0; k < kFoldHPT; ++k) {
       const uint32_t t = hk[k] < h1 ? T[hk[k] - h0] : kSkip;
       const uint64_t* row = L + (t == kSkip ? CS : t) * SW;
 #pragma unroll
@@ -548,14 +519,12 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_pipe(const PmPart* _
 // and is read there.  k_prep_fold_pipe has each lane read its hint's 32-B row
 // with ds_read_b128: random rows land on random bank slots, ~3 rows pile up
 // per slot in a 16-lane group, and the LDS array bounds the fold.  Here four
-// chunks are staged side by side: LDS line k (128 B = the 32 banks of
-// ds_read_b32) holds row k of chunks 4b..4b+3, one 32-B slot each.  In a
-// 32-lane group, lane 8s + j reads chunk slot (s + phase) & 3 and, at step t,
-// word (j + t) & 7 of its row (PM_ROT_B64 0): the 32 lanes touch 32 distinct
-// banks whatever rows their hints select, so every ds_read_b32 takes its
-// minimum 2 LDS cycles.  The default reads 8-B pairs ((j & 3) + t) & 3
-// instead (PM_ROT_B64 below).  Accumulator t of a lane always holds the same
-// word of its slice (XOR order does not matter) and is stored there at the end.
+// chunks are staged side by side: LDS line k (128 B) holds row k of chunks
+// 4b..4b+3, one 32-B slot each.  Lane l reads chunk slot (s + phase) % 4 and
+// there the 16-B halves f, then f ^ 1, of its row (s = l % 4, f = (l / 4) & 1):
+// a 16-lane ds_read_b128 group holds each (slot, half) twice, whatever rows
+// its hints select.  Accumulator t of a lane always holds the same word of
+// its slice (XOR order does not matter) and is stored there at the end.
 // The staged bytes come from the partition's fold image (PmPart::img: the
 // same 64 KB LDS image per (slice, 4 chunks), contiguous, rows past N zero),
 // a second, server-side copy of the DB laid out for this kernel (640 MB for
@@ -571,40 +540,11 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_pipe(const PmPart* _
 #ifndef PM_ROT_HPL
 #define PM_ROT_HPL 5
 #endif
-#ifndef PM_ROT_B64
-#define PM_ROT_B64 1   // 8-B LDS reads: half the reads and address selects of the 4-B form, at the
-                       // same LDS rate (lanes j and j + 4 share a bank pair when their rows have the
-                       // same parity: 2 cycles per 32-lane group, like ds_read_b32's 2 x 128 B);
-                       // 0.56-0.58 vs 0.68-0.69 ms per SIFT1M client, the fold being VALU-bound
-#endif
-#ifndef PM_ROT_B128
-#define PM_ROT_B128 1   // 16-B reads of the two halves of a row's 32-B slot: half the reads of the 8-B form
-                        // and one v_perm per (hint, chunk) for its offset instead of a 64-bit rotation
-#endif
-#ifndef PM_ROT_LW
-#define PM_ROT_LW 2   // column slices of one (partition, group) pair dealt to an XCD back to back
-                      // (64-client fold: 1 -> 31.5-31.7 ms, 2 -> 28.0-28.1, 4 -> 31.4-40.3, 5 -> 27.4-45.5)
-#endif
-#ifndef PM_ROT_ORDER
-#define PM_ROT_ORDER 1   // 1: XCD tiles of GB pairs x SB slices (below); 0: round 2's order (PM_ROT_LW)
-#endif                   // (64 clients, one box: 4 x 8 19.4 ms, 8 x 4 20.2, order 0 19.8, 16 x 2 +2 %)
 #ifndef PM_ROT_GB
-#define PM_ROT_GB 4
-#endif
+#define PM_ROT_GB 4   // XCD tile: GB (partition, group) pairs x SB slices
+#endif                // (64 clients, one box: 4 x 8 19.4 ms, 8 x 4 20.2, 16 x 2 +2 %)
 #ifndef PM_ROT_SB
 #define PM_ROT_SB 8
-#endif
-#ifndef PM_ROT_PF
-#define PM_ROT_PF 0   // L2 prefetch of the image block two buffers ahead (measured no gain once the
-                      // staging overlaps the fold: 24.2-25.4 vs 24.8-25.0 ms per 64-client launch)
-#endif
-#ifndef PM_ROT_ABL
-#define PM_ROT_ABL 0   // diagnostic builds: 1 = no LDS reads, 2 = no staging in the loop, 3 = one row per
-                       // wave (no bank conflicts), 4 = 2 and 3, 5 = no fold work at all (B128 form), 6 = 4 without
-                       // the tabT loads in the loop
-#endif
-#ifndef PM_ROT_PAIRS
-#define PM_ROT_PAIRS 1   // the B128 fold XORs two phases' rows at a time (16 VGPRs of rows in flight, not 32)
 #endif
 #ifndef PM_ROT_HPL2
 #define PM_ROT_HPL2 7   // hints per lane at CS 1,024 (2-B tiles; 128 VGPRs, no spills): 140 / 126 / 118 ms at 5 / 6 / 7
@@ -616,16 +556,15 @@ __host__ __device__ constexpr uint32_t rot_nch(uint32_t cs) { return cs == 512 ?
 template <int CS>
 __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __restrict__ parts, uint32_t E,
                                                                 uint32_t nvg, uint32_t nsl, uint32_t npv,
-                                                                uint32_t M, uint32_t K, uint32_t ngc) {
+                                                                uint32_t /* unused; bench.py pins the signature */,
+                                                                uint32_t K, uint32_t ngc) {
   constexpr uint32_t NCH = rot_nch(CS), LINE = NCH * 8, BUFW = (CS + 1) * LINE;
   constexpr int HPL = rot_hpl(CS);
-  static_assert(CS == 512 || (CS == 1024 && PM_ROT_B128 && PM_ROT_PF == 0 && PM_ROT_ABL == 0),
-                "CS 1,024: the 16-B read form only");
+  static_assert(CS == 512 || CS == 1024, "4 chunks of 512 rows or 2 of 1,024 per block");
   static_assert(CS * LINE * 4 == kRotBufBytes, "64 KB blocks");
   // static (not extern) LDS: its address is a constant the reads fold into
   // their offsets
   __shared__ __attribute__((aligned(16))) uint32_t rot_lds[2 * BUFW];
-  __shared__ uint32_t pf_lds[PM_ROT_PF ? kFoldThreads : 1];   // landing area of the L2 prefetch (never read)
   constexpr uint32_t ITEMS = CS * NCH * 2;   // 16-B staging items per buffer (NCH chunks x CS rows x 2)
   static_assert(ITEMS % kFoldThreads == 0, "whole staging items per thread");
   constexpr uint32_t G = ITEMS / kFoldThreads;
@@ -634,18 +573,12 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
   // 1,024 x HPL lane slots.  A group spans at most two clients (HB <= H),
   // and only the partition's last group has idle slots: 157 workgroups per
   // (partition, slice) for 64 SIFT1M clients instead of 3 per client (192),
-  // each staging the slice's image once.  Order: XCD x takes the (partition,
-  // group) pairs [x M, (x + 1) M); there, groups of PM_ROT_LW slices of consecutive
-  // pairs follow each other (the pairs of one partition read the same image
-  // blocks out of the XCD's L2).  (Round 1's order, (partition, group) on XCD
-  // pg % 8 with groups of 4 slices of its K clients in turn, was measured
-  // 10-15 % faster than all clients of one slice back to back.)  ngc != 0:
-  // partitions with fewer than HB hints (small configs) keep ngc groups per
-  // client instead (no mixing).
-  constexpr uint32_t LW = PM_ROT_LW, HB = kFoldThreads * HPL;
+  // each staging the slice's image once.  ngc != 0: partitions with fewer
+  // than HB hints (small configs) keep ngc groups per client instead (no
+  // mixing).
+  constexpr uint32_t HB = kFoldThreads * HPL;
   const uint32_t xcd = blockIdx.x % 8, kq = blockIdx.x / 8;
-#if PM_ROT_ORDER == 1
-  // Tiles of GB consecutive (partition, group) pairs x SB consecutive slices,
+  // Order: tiles of GB consecutive (partition, group) pairs x SB consecutive slices,
   // one tile per XCD at a time (GB * SB = its 32 CUs): a group's tabT rows are
   // read by SB workgroups and a slice's image blocks by GB workgroups out of
   // the XCD's L2.  The eight XCDs take eight consecutive pair blocks of the
@@ -662,11 +595,6 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
   const uint32_t gsup = T / (8 * nsb), m = min(8u, ngb - gsup * 8), r = T - gsup * 8 * nsb;
   const uint32_t pgv = (gsup * 8 + r % m) * GB + wt % GB;
   const uint32_t slice = (r / m) * SB + wt / GB;
-  (void)M; (void)LW;
-#else
-  const uint32_t loc = (kq / LW) % M, slice = (kq / (LW * M)) * LW + kq % LW;
-  const uint32_t pgv = xcd * M + loc;
-#endif
   if (pgv >= npv || slice >= nsl) return;   // block-uniform
   const uint32_t part = pgv / nvg, vg = pgv % nvg;
   const PmPart& P = parts[part * K];   // H, SS and the fold image are the same for every client
@@ -691,14 +619,10 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
   const uint32_t hA = cA * H;
   const uint32_t w = slice * 4, nbuf = SS / NCH;   // SetSize is a multiple of 4 (pir.go:497)
   const PM_G char* img = (const PM_G char*)P.img + (uint64_t)slice * nbuf * kRotBufBytes;
-#if PM_ROT_B128
   // 16-B reads: lane l reads chunk slot (s + phase) % NCH, halves f then f ^ 1
   // (s = l % NCH, f = (l / NCH) & 1: every ds_read_b128 lane group of 16 holds
   // each (slot, half) 8 / NCH times, MI355X_MICROARCH.md §LDS)
   const uint32_t lane = tid & 63, j = (lane / NCH) & 1, ks = lane & (NCH - 1);
-#else
-  const uint32_t lane = tid & 63, j = lane & 7, ks = (lane >> 3) & 3;
-#endif
   const uint32_t vl = v0 + tid;   // virtual hint of lane slot k: vl + k * kFoldThreads
   uint32_t acc[HPL][8];
 #pragma unroll
@@ -735,7 +659,7 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
   auto skip_idle = [&](Tile* t) {
 #pragma unroll
     for (int k = 0; k < HPL; ++k)
-      if (PM_ROT_B128 && vl + k * kFoldThreads >= v1) t[k] = ~Tile{};
+      if (vl + k * kFoldThreads >= v1) t[k] = ~Tile{};
   };
   load_tab(0, tv);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -743,33 +667,19 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
   skip_idle(tv);
   const char* lds0 = reinterpret_cast<const char*>(rot_lds);
   for (uint32_t b = 0; b < nbuf; ++b) {
-    if (b + 1 < nbuf) { if (PM_ROT_ABL != 2 && PM_ROT_ABL < 4) stage(b + 1, (b + 1) & 1); if (PM_ROT_ABL != 6) load_tab(b + 1, tn); }
-    // L2 prefetch of block b + 2 (no third LDS buffer fits): one 4-B LDS-DMA load
-    // per 128-B line by waves 0-7, issued after this iteration's staging and
-    // tabT loads, so the counted wait below leaves only it in flight
-    // (LDS-DMA intrinsics keep their order, so every staging load precedes it;
-    // a tabT load the compiler places after it is covered by its own wait)
-    // (issued by every thread, branch-free: two threads per line; past the last
-    // block it re-reads the last one)
-    if (PM_ROT_PF)
-      __builtin_amdgcn_global_load_lds(
-          (g_cvoid_t*)(img + (uint64_t)min(b + 2, nbuf - 1) * kRotBufBytes + (tid & (kFoldThreads / 2 - 1)) * 128u),
-          (lds_void_t*)(pf_lds + (tid & ~63u)), 4, 0, 0);
+    if (b + 1 < nbuf) { stage(b + 1, (b + 1) & 1); load_tab(b + 1, tn); }
     const uint32_t lb = (b & 1) * BUFW * 4;   // byte offset of this buffer
-#if PM_ROT_B128
-    {
-      uint32_t cso[NCH], psel[NCH];
+    uint32_t cso[NCH], psel[NCH];
 #pragma unroll
-      for (uint32_t ph = 0; ph < NCH; ++ph) {
-        const uint32_t sl = (ks + ph) & (NCH - 1);
-        cso[ph] = lb + sl * 32 + 16 * j;
-        psel[ph] = 0x0c0c0000u | ((2 * sl + 1) << 8) | (2 * sl);   // v_perm: tile word sl, zero-extended
-      }
+    for (uint32_t ph = 0; ph < NCH; ++ph) {
+      const uint32_t sl = (ks + ph) & (NCH - 1);
+      cso[ph] = lb + sl * 32 + 16 * j;
+      psel[ph] = 0x0c0c0000u | ((2 * sl + 1) << 8) | (2 * sl);   // v_perm: tile word sl, zero-extended
+    }
 #pragma unroll
-      for (int k = 0; k < (PM_ROT_ABL == 5 ? 0 : HPL); ++k) {
-#if PM_ROT_PAIRS
+    for (int k = 0; k < HPL; ++k) {
 #pragma unroll
-       for (uint32_t p0 = 0; p0 < NCH; p0 += 2) {   // two phases' rows in flight, then their XOR
+      for (uint32_t p0 = 0; p0 < NCH; p0 += 2) {   // two phases' rows in flight (16 VGPRs), then their XOR
         uint32_t v[2][8];
 #pragma unroll
         for (uint32_t pp = 0; pp < 2; ++pp) {
@@ -777,7 +687,7 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
           uint32_t o;
           if constexpr (NCH == 4) o = __builtin_amdgcn_perm(tv[k].y, tv[k].x, psel[ph]);
           else o = __builtin_amdgcn_perm(0u, tv[k], psel[ph]);
-          o = min(o, (uint32_t)CS);
+          o = min(o, (uint32_t)CS);   // kSkip -> zero line
           const uint32_t a = o * (LINE * 4) + cso[ph];
           const uint4 x0 = *reinterpret_cast<const uint4*>(lds0 + a);
           const uint4 x1 = *reinterpret_cast<const uint4*>(lds0 + (a ^ 16u));
@@ -785,86 +695,14 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
           v[pp][4] = x1.x; v[pp][5] = x1.y; v[pp][6] = x1.z; v[pp][7] = x1.w;
         }
 #pragma unroll
-        for (int t = 0; t < 8; ++t) acc[k][t] = xor3(acc[k][t], v[0][t], v[1][t]);
-       }
-       continue;
-#endif
-        uint32_t v[NCH][8];
-#pragma unroll
-        for (uint32_t ph = 0; ph < NCH; ++ph) {
-          uint32_t o;
-          if constexpr (NCH == 4) o = __builtin_amdgcn_perm(tv[k].y, tv[k].x, psel[ph]);
-          else o = __builtin_amdgcn_perm(0u, tv[k], psel[ph]);
-          o = min(o, (uint32_t)CS);   // kSkip -> zero line
-          if (PM_ROT_ABL == 3 || PM_ROT_ABL == 4 || PM_ROT_ABL == 6) o = __builtin_amdgcn_readfirstlane(o);   // one row per wave: no conflicts
-          const uint32_t a = o * (LINE * 4) + cso[ph];
-          const uint4 x0 = *reinterpret_cast<const uint4*>(lds0 + a);
-          const uint4 x1 = *reinterpret_cast<const uint4*>(lds0 + (a ^ 16u));
-          v[ph][0] = x0.x; v[ph][1] = x0.y; v[ph][2] = x0.z; v[ph][3] = x0.w;
-          v[ph][4] = x1.x; v[ph][5] = x1.y; v[ph][6] = x1.z; v[ph][7] = x1.w;
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          if constexpr (NCH == 4) acc[k][t] = xor3(xor3(acc[k][t], v[0][t], v[1][t]), v[2][t], v[3][t]);
-          else acc[k][t] = xor3(acc[k][t], v[0][t], v[1][t]);
-        }
+        for (int t = 0; t < 8; ++t)   // v_bitop3_b32 0x96 = a ^ b ^ c (gfx950): two XORs per instruction
+          acc[k][t] = xor3(acc[k][t], v[0][t], v[1][t]);
       }
     }
-    if (false)
-#endif
-    if constexpr (NCH == 4) {
-    // per phase: this lane's chunk slot and its word base in the line
-    uint32_t cso[4];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
 #pragma unroll
-    for (uint32_t ph = 0; ph < 4; ++ph) cso[ph] = lb + ((ks + ph) & 3) * 32 + (PM_ROT_B64 ? 8 * (j & 3) : 4 * j);
-#pragma unroll
-    for (int k = 0; k < (PM_ROT_ABL == 1 ? 0 : HPL); ++k) {
-      const bool hv = vl + k * kFoldThreads < v1;   // lane slots past the group: zero line
-      // the 4 offsets in phase order: rotate the 64-bit tile right by 16 ks
-      const uint64_t t64 = ((uint64_t)tv[k].y << 32) | tv[k].x;
-      const uint32_t sh = 16 * ks;
-      const uint64_t rot = sh ? ((t64 >> sh) | (t64 << (64 - sh))) : t64;
-      uint32_t v[4][8];
-#pragma unroll
-      for (uint32_t ph = 0; ph < 4; ++ph) {
-        uint32_t o = (uint32_t)(rot >> (16 * ph)) & 0xffffu;
-        o = hv ? min(o, (uint32_t)CS) : (uint32_t)CS;   // kSkip -> the zero line
-        // word (j + t) & 7 of the slot: base + 4t, or base + 4t - 32 where
-        // j + t >= 8 (a per-lane select; 4t is the instruction's offset)
-        const uint32_t a = o * (LINE * 4) + cso[ph], a2 = a - 32;
-        if (PM_ROT_B64) {   // word pair ((j & 3) + t) & 3: 8-B reads, lanes j and j + 4 2-way on a bank pair
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const uint64_t x = *reinterpret_cast<const uint64_t*>(lds0 + (((j & 3) < 4u - t) ? a : a2) + 8 * t);
-            v[ph][2 * t] = (uint32_t)x;
-            v[ph][2 * t + 1] = (uint32_t)(x >> 32);
-          }
-        } else {
-#pragma unroll
-          for (int t = 0; t < 8; ++t)
-            v[ph][t] = *reinterpret_cast<const uint32_t*>(lds0 + ((j < 8u - t) ? a : a2) + 4 * t);
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < 8; ++t)   // v_bitop3_b32 0x96 = a ^ b ^ c (gfx950): two XORs per instruction
-        acc[k][t] = xor3(xor3(acc[k][t], v[0][t], v[1][t]), v[2][t], v[3][t]);
-    }
-    }
-    if (PM_ROT_PF) {
-      // the prefetch may stay in flight: counted wait, then a raw barrier
-      // (__syncthreads' fence would wait for every load, the prefetch included)
-      asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < HPL; ++k) {
-      if constexpr (NCH == 4) tv[k] = PM_ROT_ABL == 6 ? tv[k] + u32x2{1u, 3u} : tn[k];
-      else tv[k] = tn[k];
-    }
+    for (int k = 0; k < HPL; ++k) tv[k] = tn[k];
     skip_idle(tv);
   }
 #pragma unroll
@@ -876,8 +714,7 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
     PM_G uint32_t* dst = reinterpret_cast<PM_G uint32_t*>(par + w);
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-      PM_G uint32_t* const d = dst + (PM_ROT_B128 ? 4 * (j ^ (t >> 2)) + (t & 3)
-                                      : PM_ROT_B64 ? 2 * (((j & 3) + t / 2) & 3) + (t & 1) : (j + t) & 7);
+      PM_G uint32_t* const d = dst + 4 * (j ^ (t >> 2)) + (t & 3);
       if (PM_PREP_NT) __builtin_nontemporal_store(acc[k][t], d);
       else *d = acc[k][t];
     }
@@ -1264,15 +1101,13 @@ int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint
       const uint64_t HB = (uint64_t)kFoldThreads * rot_hpl(maxCS);
       const uint32_t ngc = minH >= HB ? 0u : (uint32_t)cdiv(maxH, HB);
       const uint32_t nvg = ngc ? K * ngc : (uint32_t)cdiv((uint64_t)K * maxH, HB), npv = (np / K) * nvg;
-      const uint32_t M = cdiv(npv, 8);
-      const uint32_t grid = PM_ROT_ORDER == 1
-                                ? 8 * cdiv((uint64_t)cdiv(npv, PM_ROT_GB) * cdiv(nsl, PM_ROT_SB), 8) * PM_ROT_GB * PM_ROT_SB
-                                : 8 * M * cdiv(nsl, PM_ROT_LW) * PM_ROT_LW;
+      // whole tiles of GB pairs x SB slices, dealt over the 8 XCDs (the kernel's fifth parameter is unused)
+      const uint32_t grid = 8 * cdiv((uint64_t)cdiv(npv, PM_ROT_GB) * cdiv(nsl, PM_ROT_SB), 8) * PM_ROT_GB * PM_ROT_SB;
       if (maxCS == 512) {
-        hipLaunchKernelGGL(k_prep_fold_rot<512>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, M, K, ngc);
+        hipLaunchKernelGGL(k_prep_fold_rot<512>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, 0u, K, ngc);
         return FOLD_ROT512;
       }
-      hipLaunchKernelGGL(k_prep_fold_rot<1024>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, M, K, ngc);
+      hipLaunchKernelGGL(k_prep_fold_rot<1024>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, 0u, K, ngc);
       return FOLD_ROT1024;
     }
     const uint32_t nb = maxCS == 512 ? PM_FOLD_NB512 : 3;   // LDS buffers: <= 150 KB

@@ -1423,19 +1423,9 @@ __global__ void __launch_bounds__(kResolveBlockG) k_match_resolve(PmStep S) {
 // predictions of resolve_role's staged prologue (in-chunk index, re-evaluation
 // values) meanwhile.  Results are identical to k_match_resolve's.
 // Measured alone at the bench's 64-session groups (k_match_resolve_s<2,256>):
-// 19.1-19.3 us with the defaults; 19.7 with all 6 sub-queries' search rows in
-// one round trip (PM_MR_G 0: 8 per round trip for NU <= 2, 6 for NU 4, 82
-// VGPRs and SGPR spills), with or without the candidates' tags loaded by the
-// matching wave (PM_MR_TAGPF 1) instead of by wave 0 after the barrier.
-#ifndef PM_MR_TAGPF
-#define PM_MR_TAGPF 0
-#endif
+// 19.1-19.3 us.
 #ifndef PM_MR_G
-#define PM_MR_G 8       // search rows of 8 / NU sub-queries per round trip (0: see above)
-#endif
-#ifndef PM_MR_EARLY
-#define PM_MR_EARLY 1   // k_match_resolve_s: row block 0 first, the rest only where fewer than two matches
-                        // (+0.6 %, ABBA, profiles/r05/ab/match_early_exit.log)
+#define PM_MR_G 8       // search rows of 8 / NU sub-queries per round trip
 #endif
 #ifndef PM_MR_NTLOAD
 #define PM_MR_NTLOAD 1   // k_match_resolve_s' search-row loads nontemporal: streamed, not kept in the Infinity Cache
@@ -1459,12 +1449,11 @@ __global__ void __launch_bounds__(NT) k_match_resolve_s(PmStep S) {
   if (PM_CHAIN_PRIO) __builtin_amdgcn_s_setprio(PM_CHAIN_PRIO);
   // G sub-queries' search rows in flight together (the usual 6 per partition:
   // one round trip); 2 * G * NU <= 64 candidates per wave, one per lane
-  constexpr int NW = NT / 64, G = PM_MR_G ? PM_MR_G / NU : NU <= 2 ? 8 : NU == 4 ? 6 : 8 / NU;
+  constexpr int NW = NT / 64, G = PM_MR_G / NU;
   static_assert(2 * G * NU <= 64, "one lane per candidate");
   __shared__ ResolveLds<3> L;
-  // each (sub-query, row block, wave): first two matches, their tags and program points
-  __shared__ uint32_t s_m[kSpecSubs][NU][NW][2], s_mt[kSpecSubs][NU][NW][PM_MR_TAGPF ? 2 : 1],
-      s_mp[kSpecSubs][NU][NW][PM_MR_TAGPF ? 2 : 1];
+  // each (sub-query, row block, wave): first two matches
+  __shared__ uint32_t s_m[kSpecSubs][NU][NW][2];
   const uint32_t p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   MRST(0);
   // the partition record is loaded with the descriptor range (its field in the
@@ -1579,22 +1568,16 @@ __global__ void __launch_bounds__(NT) k_match_resolve_s(PmStep S) {
         if (lane == 2 * (g * NU + u) + 1) cand = a1;
       }
     }
-    // the candidates' tags and program points, one lane each, all in flight
-    // together (the resolver's chain and the set expansion read them from LDS)
-    uint32_t ct = 0, cp = 0;
-    if (PM_MR_TAGPF && cand != kNone) { ct = P.tag[cand]; cp = P.pp[cand]; }
     const uint32_t qg = lane / (2 * NU), qu = (lane / 2) % NU, qi = lane % 2;
-    if (lane < 2 * G * NU && j0 + qg < n && ((umask >> qu) & 1) && ((jmask >> (j0 + qg)) & 1)) {
+    if (lane < 2 * G * NU && j0 + qg < n && ((umask >> qu) & 1) && ((jmask >> (j0 + qg)) & 1))
       s_m[j0 + qg][qu][wave][qi] = cand;
-      if (PM_MR_TAGPF) { s_mt[j0 + qg][qu][wave][qi % 2] = ct; s_mp[j0 + qg][qu][wave][qi % 2] = cp; }
-    }
   }
   };
-#if PM_MR_EARLY
   // Row block 0 first (hints 0 .. 8 NT - 1); the other blocks only for the
   // sub-queries with fewer than two matches there (the candidates are the
   // first two in hint order): ~9 % of them at SIFT1M's PH, and ~40 % fewer
   // search-row bytes per step for one more round trip where any needs them
+  // (+0.6 % against every block at once, ABBA, profiles/r05/ab/match_early_exit.log)
   match_pass(1u, ~0ull);
   if (NU > 1) {
     for (uint32_t x = tid; x < n * (NU - 1) * NW * 2; x += NT) {   // the other blocks' slots: none yet
@@ -1610,9 +1593,6 @@ __global__ void __launch_bounds__(NT) k_match_resolve_s(PmStep S) {
     }
     if (need) match_pass(((1u << NU) - 1) & ~1u, need);   // block-uniform (from LDS)
   }
-#else
-  match_pass((1u << NU) - 1, ~0ull);
-#endif
   MRST(2);
   __syncthreads();
   MRST(3);
@@ -1626,12 +1606,11 @@ __global__ void __launch_bounds__(NT) k_match_resolve_s(PmStep S) {
           for (int i = 0; i < 2; ++i) {
             const uint32_t h = s_m[j][u][w][i];
             if (h == kNone || c2 != kNone) continue;
-            const uint32_t ti = PM_MR_TAGPF ? i : 0;
-            if (c1 == kNone) { c1 = h; t1 = s_mt[j][u][w][ti]; p1 = s_mp[j][u][w][ti]; }
-            else { c2 = h; t2 = s_mt[j][u][w][ti]; p2 = s_mp[j][u][w][ti]; }
+            if (c1 == kNone) c1 = h;
+            else c2 = h;
           }
-      if (!PM_MR_TAGPF && c1 != kNone) { t1 = P.tag[c1]; p1 = P.pp[c1]; }
-      if (!PM_MR_TAGPF && c2 != kNone) { t2 = P.tag[c2]; p2 = P.pp[c2]; }
+      if (c1 != kNone) { t1 = P.tag[c1]; p1 = P.pp[c1]; }
+      if (c2 != kNone) { t2 = P.tag[c2]; p2 = P.pp[c2]; }
     }
     L.s_c1[j] = c1; L.s_c2[j] = c2; L.s_t1[j] = t1; L.s_p1[j] = p1; L.s_t2[j] = t2; L.s_p2[j] = p2;
   }
@@ -1732,60 +1711,18 @@ __device__ __forceinline__ uint64_t row_csum(const PmStep& S, const RB& row, boo
   return x;
 }
 
-// Result publication into pinned (fine-grained) host memory.  The default
-// (PM_PUBLISH 0): lane 0 stores the header as soon as the row is final in
-// LDS, and no wave waits for its row stores to be acknowledged.  The token is
-// a progress mark only: the host takes the step's results after the step's
-// completion event (system-scope release after the last kernel, pm_engine.cpp
-// wait_step), and checks the row hash there as an assertion (pm_internal.h
-// PmOutHdr).  (4: row stores acknowledged before a workgroup barrier and the
-// header, as in round 1 — rows still arrive after the token, measured.)  Two
-// in-kernel ordered forms, both measured with 0 torn rows in 49M but 2.8x /
-// 4.4x the kernel time, are kept as build options:
-//   1: lane 0 stores the other header fields, then a SYSTEM-scope release
-//      (buffer_wbl2 sc0 sc1: the XCD L2's dirty lines, every wave's included,
-//      are written back) and an explicit s_waitcnt vmcnt(0) — inline asm, so
-//      the compiler cannot drop the wait after the write-back
-//      (MI355X_MICROARCH.md "Compiler hazard") — then the token as ONE 8-byte
-//      system-scope store {dist, token};
-//   3: every row and header word stored write-through at system scope
-//      (sc0 sc1), each wave's stores acknowledged before the barrier, the
-//      token stored after lane 0's header stores are acknowledged.
-#ifndef PM_PUBLISH
-#define PM_PUBLISH 0
-#endif
-__device__ __forceinline__ void row_store(PM_G uint64_t* p, uint64_t v) {
-  if (PM_PUBLISH >= 2) __hip_atomic_store((uint64_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  else *p = v;
-}
+// Result publication into pinned (fine-grained) host memory: lane 0 stores
+// the header as soon as the row is final in LDS, and no wave waits for its row
+// stores to be acknowledged.  The token is a progress mark only: the host
+// takes the step's results after the step's completion event (system-scope
+// release after the last kernel, pm_engine.cpp wait_step), and checks the row
+// hash there as an assertion (pm_internal.h PmOutHdr).  (The in-kernel ordered
+// forms that were measured are in DESIGN.md, Retired experiments.)
+__device__ __forceinline__ void row_store(PM_G uint64_t* p, uint64_t v) { *p = v; }
 __device__ __forceinline__ void publish_hdr(const PmStep& S, uint32_t s, uint32_t status, uint32_t ref,
                                             float d, uint64_t csum) {
   PM_G PmOutHdr* h = S.hdr_h + s;
-  if (PM_PUBLISH == 0) {   // lane 0 (it holds d and csum) as soon as the row is final in LDS
-    if (threadIdx.x == 0) *h = PmOutHdr{status, ref, d, S.token, csum + S.token * kCsumMix, 0};
-    return;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const uint64_t tok = ((uint64_t)S.token << 32) | __float_as_uint(d);   // {dist, token}: bytes 8..15
-  if (PM_PUBLISH == 4) {   // round 1's drained form: row stores acknowledged, then the plain header
-    *h = PmOutHdr{status, ref, d, S.token, csum + S.token * kCsumMix, 0};
-    return;
-  }
-  PM_G uint64_t* w = reinterpret_cast<PM_G uint64_t*>(h);
-  if (PM_PUBLISH == 3) {   // every byte written through at system scope: no L2 write-back needed
-    __hip_atomic_store((uint64_t*)w, ((uint64_t)ref << 32) | status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store((uint64_t*)(w + 2), csum + S.token * kCsumMix, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store((uint64_t*)(w + 1), tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    return;
-  }
-  w[0] = ((uint64_t)ref << 32) | status;
-  w[2] = csum + S.token * kCsumMix;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __hip_atomic_store((uint64_t*)(w + 1), tok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (threadIdx.x == 0) *h = PmOutHdr{status, ref, d, S.token, csum + S.token * kCsumMix, 0};   // lane 0 holds d and csum
 }
 
 // What a k_answer workgroup does for its sub-query.
@@ -2513,7 +2450,7 @@ __device__ __forceinline__ bool ansp_gathers(const AnsQ& a) {
   return a.mode == A_FINAL || a.mode == A_CHAINED || a.mode == A_DUMMY;
 }
 // A workgroup owns sub-queries s_k = blockIdx.x + k * gridDim.x (grid =
-// nsub / PM_ANSWER_PK on the host, 2 by default) in two operand slots: while
+// nsub / PM_ANSWER_PK_MAX on the host, 2 by default) in two operand slots: while
 // slot c gathers, slot c ^ 1 holds the next sub-query's record and query set;
 // the next one's first row batch is issued before slot c's reduction, decode
 // and publication, and slot c is refilled (record + query set of s_{k+2})
@@ -2552,12 +2489,8 @@ __device__ __forceinline__ bool ansp_turn(const PmStep& S, AnswerPLds<NT>& L, An
   return true;
 }
 #ifndef PM_ANSWER_PK_MAX
-#define PM_ANSWER_PK_MAX 2   // sub-queries per k_answer_p workgroup the kernel is built for (the host's PM_ANSWER_PK is
-                             // clamped to it); 3 spills ~150 VGPRs at 80
-#endif
-#ifndef PM_ANSWER_P_TAIL
-#define PM_ANSWER_P_TAIL 0   // k_answer_p's grid capped at PM_ANSWER_P_TAIL workgroups; the sub-queries past two
-                             // per workgroup are answered one at a time at the end (diagnostic build)
+#define PM_ANSWER_PK_MAX 2   // sub-queries per k_answer_p workgroup (the host's grid is nsub / PM_ANSWER_PK_MAX);
+                             // 3 spills ~150 VGPRs at 80
 #endif
 #ifndef PM_ANSWER_P_WAVES
 #define PM_ANSWER_P_WAVES 6   // min waves per SIMD: <= 80 VGPRs (the next sub-query's row batch stays live through
@@ -2590,31 +2523,6 @@ __global__ void __launch_bounds__(NT, PM_ANSWER_P_WAVES) k_answer_p(PmStep S) {
   if (!ansp_turn<W, NT, KG, 1>(S, L, q, qpv, g, 1, false)) return;
   if (PM_ANSWER_PK_MAX > 2 && !ansp_turn<W, NT, KG, 0>(S, L, q, qpv, g, 2, false)) return;
   if (PM_ANSWER_PK_MAX > 3) ansp_turn<W, NT, KG, 1>(S, L, q, qpv, g, 3, false);
-#if PM_ANSWER_P_TAIL
-  // a grid of fewer workgroups than sub-query pairs (PM_ANSWER_P_TAIL: the
-  // host caps it at the resident slots): the rest, one at a time, unpipelined
-  for (uint32_t s = blockIdx.x + 2 * G; s < ns; s += G) {
-    AnsQ t;
-    uint4 tq;
-    ansp_record<W, NT>(S, s, t, tq);
-    t.mode = answer_mode(t.r);
-    ansp_decode_ops<W, NT>(S, t);
-    ansp_set(S, t, tq, L.qo[0]);
-    __syncthreads();
-    AnsGather<W, NT, KG> gt;
-    gt.init(S.E);
-    if (ansp_gathers(t)) {
-      const PmPart& P = S.parts[t.part];
-      const uint32_t nb = gt.batches(P);
-      for (uint32_t b = 0; b < nb; ++b) {
-        gt.load(S, P, L.qo[0], b);
-        gt.fold();
-      }
-      gt.reduce(L, S.E);
-    }
-    ansp_epilogue<W, NT>(S, t, L);
-  }
-#endif
 }
 
 // ---- k_gather: the server's XOR gather of wide sets, split ----------------
@@ -2887,16 +2795,11 @@ void step_match_resolve(hipStream_t st, const PmStep& S, const StepOpts& O, bool
                         uint32_t max_sub_per_part, PmEvents ev) {
   // the one-round-trip form where its shapes hold (PM_MATCH_RESOLVE=2: always the general one)
   const bool small = step_match_resolve_small(O, ph8, maxPH, max_sub_per_part);
-  // workgroup size (PM_MR_NT): 256 leaves the GPU's wave slots to the other
-  // groups' kernels while wave 0 runs the chain
-  static const int nt = [] { const char* e = getenv("PM_MR_NT"); return e ? atoi(e) : 256; }();
-  if (small && nt == 128 && maxPH <= 8u * 128 * 4)
-    PM_LAUNCH(ev, (k_match_resolve_s<4, 128>), dim3(S.np), dim3(128), st, S);
-  else if (small && nt == 128 && maxPH <= 8u * 128 * 8)
-    PM_LAUNCH(ev, (k_match_resolve_s<8, 128>), dim3(S.np), dim3(128), st, S);
-  else if (small && nt == 256 && maxPH <= 8u * 256 * 2)
+  // 256-thread workgroups where they hold the partition's hints: they leave
+  // the GPU's wave slots to the other groups' kernels while wave 0 runs the chain
+  if (small && maxPH <= 8u * 256 * 2)
     PM_LAUNCH(ev, (k_match_resolve_s<2, 256>), dim3(S.np), dim3(256), st, S);
-  else if (small && nt == 256 && maxPH <= 8u * 256 * 4)
+  else if (small && maxPH <= 8u * 256 * 4)
     PM_LAUNCH(ev, (k_match_resolve_s<4, 256>), dim3(S.np), dim3(256), st, S);
   else if (small && maxPH <= 8u * kResolveBlockG)
     PM_LAUNCH(ev, (k_match_resolve_s<1, kResolveBlockG>), dim3(S.np), dim3(kResolveBlockG), st, S);
@@ -2908,8 +2811,7 @@ void step_match_resolve(hipStream_t st, const PmStep& S, const StepOpts& O, bool
 bool step_qset_ok(const PmStep& S, const StepOpts& O, bool lds, bool ph8, uint32_t maxPH,
                   uint32_t max_sub_per_part, uint32_t maxSS) {
   const int mode = O.match_resolve;
-  static const int qs = [] { const char* e = getenv("PM_QSET"); return e ? atoi(e) : 1; }();
-  return qs && mode == 1 && step_match_resolve_ok(S, O, lds) && max_sub_per_part <= kSpecSubs && ph8 &&
+  return mode == 1 && step_match_resolve_ok(S, O, lds) && max_sub_per_part <= kSpecSubs && ph8 &&
          maxPH <= 16u * kResolveBlockG && maxSS <= kSmallSS && S.nsplit <= 1;
 }
 void step_resolve(hipStream_t st, const PmStep& S, bool lds, PmEvents ev) {
@@ -2936,11 +2838,9 @@ void step_answer(hipStream_t st, const PmStep& S, uint32_t maxSS, PmEvents ev) {
   static_assert(2u * kAnsPNT >= kSmallE, "k_answer_p's gather slices must cover a kSmallE row");
   if (pair && S.qset && S.nsplit <= 1 && maxSS <= kSmallSS && S.E % 2 == 0 && S.E <= kSmallE &&
       (S.E & ~3u) <= 2u * kAnsPNT && S.nsub >= 2 * 256) {
-    // sub-queries per workgroup (the grid is nsub / pk; 2: every workgroup of a
+    // PM_ANSWER_PK_MAX sub-queries per workgroup (2: every workgroup of a
     // 6,144-sub-query step resident at once)
-    static const uint32_t pk = [] { const char* e = getenv("PM_ANSWER_PK"); return std::min(e && atoi(e) > 1 ? (uint32_t)atoi(e) : (uint32_t)PM_ANSWER_PK_MAX, (uint32_t)PM_ANSWER_PK_MAX); }();
-    uint32_t grid = (S.nsub + pk - 1) / pk;
-    if (PM_ANSWER_P_TAIL) grid = std::min(grid, (uint32_t)PM_ANSWER_P_TAIL);
+    const uint32_t grid = (S.nsub + PM_ANSWER_PK_MAX - 1) / PM_ANSWER_PK_MAX;
     PM_LAUNCH(ev, (k_answer_p<2, kAnsPNT>), dim3(grid), dim3(kAnsPNT), st, S);
     return;
   }

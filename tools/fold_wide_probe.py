@@ -20,5 +20,5 @@ for _ in range(reps):
 ctx.timing(False)
 for k in ("prep_offsets", "prep_fold", "prep_repl"):
     n, ms, by = ctx.timing_get(k)
-    print(f"{shape} {os.environ.get('PM_FOLD_WIDE', '1')} {k}: {ms / max(n, 1):.3f} ms/launch over {n}"
+    print(f"{shape} {k}: {ms / max(n, 1):.3f} ms/launch over {n}"
           + (f", {by / n / (ms / n / 1e3) / 1e12:.2f} T units/s" if n and ms else ""), flush=True)
