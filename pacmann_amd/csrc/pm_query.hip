@@ -2496,10 +2496,8 @@ __device__ __forceinline__ bool ansp_turn(const PmStep& S, AnswerPLds<NT>& L, An
 #define PM_ANSWER_P_WAVES 6   // min waves per SIMD: <= 80 VGPRs (the next sub-query's row batch stays live through
                               // an epilogue); 12 two-wave workgroups per CU = the 3,072 of a 6,144-sub-query step
 #endif
-template <int W, int NT>
-__global__ void __launch_bounds__(NT, PM_ANSWER_P_WAVES) k_answer_p(PmStep S) {
-  __shared__ AnswerPLds<NT> L;
-  constexpr int KG = PM_ANSWER_KG;
+template <int W, int NT, int KG>
+__device__ __forceinline__ void answer_p_body(const PmStep& S, AnswerPLds<NT>& L) {
   AnsQ q[2];
   uint4 qpv[2];
   const uint32_t ns = S.nsub, G = gridDim.x;
@@ -2523,6 +2521,22 @@ __global__ void __launch_bounds__(NT, PM_ANSWER_P_WAVES) k_answer_p(PmStep S) {
   if (!ansp_turn<W, NT, KG, 1>(S, L, q, qpv, g, 1, false)) return;
   if (PM_ANSWER_PK_MAX > 2 && !ansp_turn<W, NT, KG, 0>(S, L, q, qpv, g, 2, false)) return;
   if (PM_ANSWER_PK_MAX > 3) ansp_turn<W, NT, KG, 1>(S, L, q, qpv, g, 3, false);
+}
+template <int W, int NT>
+__global__ void __launch_bounds__(NT, PM_ANSWER_P_WAVES) k_answer_p(PmStep S) {
+  __shared__ AnswerPLds<NT> L;
+  answer_p_body<W, NT, PM_ANSWER_KG>(S, L);
+}
+// The 5-wave form: at most 88 VGPRs, so that five answer waves use 440 of a
+// SIMD's 512 and one 64-VGPR wave of a chain kernel (k_match_resolve_s,
+// k_team_round) always fits beside the other teams' answers, which 6 x 80 =
+// 480 does not allow; 10 workgroups per CU.  The registers carry a seventh row
+// per gather batch: 20 waves x 7 rows in flight per CU against 24 x 6.
+constexpr int kAnsP5KG = 7;
+template <int W, int NT>
+__global__ void __launch_bounds__(NT, 5) __attribute__((amdgpu_num_vgpr(88))) k_answer_p5(PmStep S) {
+  __shared__ AnswerPLds<NT> L;
+  answer_p_body<W, NT, kAnsP5KG>(S, L);
 }
 
 // ---- k_gather: the server's XOR gather of wide sets, split ----------------
@@ -2726,8 +2740,9 @@ static inline unsigned cdiv(uint64_t a, uint64_t b) { return (unsigned)((a + b -
 constexpr int kOptUnset = INT32_MIN;
 static int env_int(const char* name, int def) { const char* e = getenv(name); return e ? atoi(e) : def; }
 static const int env_match_part = env_int("PM_MATCH_PART", -1), env_match_part8 = env_int("PM_MATCH_PART8", 1),
-                 env_match_resolve = env_int("PM_MATCH_RESOLVE", 1);
-static std::atomic<int> ov_match_part{kOptUnset}, ov_match_part8{kOptUnset}, ov_match_resolve{kOptUnset};
+                 env_match_resolve = env_int("PM_MATCH_RESOLVE", 1), env_answer_waves = env_int("PM_ANSWER_WAVES", 0);
+static std::atomic<int> ov_match_part{kOptUnset}, ov_match_part8{kOptUnset}, ov_match_resolve{kOptUnset},
+    ov_answer_waves{kOptUnset};
 static int opt(const std::atomic<int>& ov, int env) {
   const int v = ov.load(std::memory_order_relaxed);
   return v != kOptUnset ? v : env;
@@ -2742,7 +2757,8 @@ StepOpts step_opts() {
 int set_option(const char* name, int value) {
   std::atomic<int>* o = !strcmp(name, "match_part") ? &ov_match_part
                       : !strcmp(name, "match_part8") ? &ov_match_part8
-                      : !strcmp(name, "match_resolve") ? &ov_match_resolve : nullptr;
+                      : !strcmp(name, "match_resolve") ? &ov_match_resolve
+                      : !strcmp(name, "answer_waves") ? &ov_answer_waves : nullptr;
   if (!o) return -1;
   o->store(value <= -2 ? kOptUnset : value, std::memory_order_relaxed);
   return 0;
@@ -2841,7 +2857,14 @@ void step_answer(hipStream_t st, const PmStep& S, uint32_t maxSS, PmEvents ev) {
     // PM_ANSWER_PK_MAX sub-queries per workgroup (2: every workgroup of a
     // 6,144-sub-query step resident at once)
     const uint32_t grid = (S.nsub + PM_ANSWER_PK_MAX - 1) / PM_ANSWER_PK_MAX;
-    PM_LAUNCH(ev, (k_answer_p<2, kAnsPNT>), dim3(grid), dim3(kAnsPNT), st, S);
+    // PM_ANSWER_WAVES / "answer_waves": 6 = the 80-VGPR form, 5 = k_answer_p5,
+    // 0 = chosen by shape: the 5-wave form for entries of at most 80 words
+    // (SIFT1M; MS-MARCO's 100-word entries were not compared and stay at 6)
+    const int waves = opt(ov_answer_waves, env_answer_waves);
+    if (waves == 5 || (waves == 0 && S.E <= 80))
+      PM_LAUNCH(ev, (k_answer_p5<2, kAnsPNT>), dim3(grid), dim3(kAnsPNT), st, S);
+    else
+      PM_LAUNCH(ev, (k_answer_p<2, kAnsPNT>), dim3(grid), dim3(kAnsPNT), st, S);
     return;
   }
   if (nt && S.nsplit <= 1 && maxSS <= kSmallSS && S.E <= kSmallE) {
