@@ -429,6 +429,83 @@ extern "C" int pm_timing_get(pm_ctx* c, const char* name, uint64_t* launches, do
 }
 
 // ---------------------------------------------------------------------------
+// One step's scratch (k_match -> k_resolve -> [k_gather] -> k_answer), held by
+// an Engine for its own steps and by a StepGroup for its shared ones.  The
+// device buffers are sized by reserve() for nsub sub-queries over np
+// partitions; part_x (split gather), stamps (stamp builds) and the pinned
+// descriptor / result buffers are reserved where a step needs them.
+// ---------------------------------------------------------------------------
+struct StepBufs {
+  DevBuf subs_d, sb_d, bits, cand, meta, spec, res_d, ans, part_x, stamps;
+  HostBuf desc_h, out_h;
+  int reserve(uint32_t nsub, uint32_t np, uint32_t words, uint32_t cblk, uint64_t E) {
+    CHK(subs_d.reserve(nsub * sizeof(PmSub)));
+    CHK(sb_d.reserve((np + 1) * 4));
+    CHK(bits.reserve((uint64_t)nsub * words * 8));
+    CHK(cand.reserve((uint64_t)nsub * cblk * 6 * 4));
+    CHK(meta.reserve((uint64_t)nsub * 2 * 4));
+    CHK(spec.reserve((uint64_t)nsub * 64 * 4));
+    CHK(res_d.reserve(nsub * sizeof(PmRes)));
+    CHK(ans.reserve((uint64_t)nsub * E * 8));
+    return 0;
+  }
+  void fill(PmStep& S, uint32_t words, uint32_t cblk) const {
+    S.subs = subs_d.as<PmSub>();
+    S.sb = sb_d.as<uint32_t>();
+    S.bits = bits.as<uint64_t>();
+    S.cand = cand.as<uint32_t>();
+    S.meta = meta.as<uint32_t>();
+    S.spec = spec.as<uint32_t>();
+    S.res = res_d.as<PmRes>();
+    S.ans = ans.as<uint64_t>();
+    S.words = words;
+    S.cblk = cblk;
+  }
+};
+// A step's results for nsub sub-queries in one buffer (pinned, or device memory
+// where they stay on the GPU): the headers, then the rows.
+static inline size_t step_out_bytes(uint32_t nsub, uint64_t E) { return nsub * sizeof(PmOutHdr) + (size_t)nsub * E * 8; }
+static inline void step_out(PmStep& S, void* out, uint32_t nsub) {
+  S.hdr_h = (PmOutHdr*)out;
+  S.rows_h = (uint64_t*)((char*)out + nsub * sizeof(PmOutHdr));
+}
+// The step's token: 0 never marks a published header.
+static inline uint32_t next_token(uint32_t& token) {
+  if (++token == 0) ++token;
+  return token;
+}
+// The row words [pf_w0, pf_w1) the consumer reads next (bytes [pf_off, pf_off +
+// pf_len) of each E-word row): checksummed in the header (PmOutHdr).
+static inline void step_read_window(PmStep& S, size_t pf_off, size_t pf_len, uint64_t E) {
+  const size_t off = std::min<size_t>(pf_off, E * 8);
+  const size_t end = std::min<size_t>(E * 8, off + std::min<size_t>(pf_len, E * 8));
+  S.pf_w0 = (uint32_t)(off / 8);
+  S.pf_w1 = (uint32_t)((end + 7) / 8);
+}
+// PmStep::rows_partial for results the host reads: only the window's words are
+// sent when the caller reads no others, unless a diagnostic re-reads whole rows.
+static inline uint32_t host_rows_partial(const pm_ctx* c, bool partial) {
+  return partial && !c->verify_rows && !c->debug_cache ? 1u : 0u;
+}
+#if defined(PM_STEP_STAMPS) || defined(PM_MR_STAMPS) || defined(PM_ANSWER_STAMPS)
+// Stamp builds: drain st, then append `hdr` and the first `count` words of
+// `buf` to the file at `path`.
+static int dump_stamps(hipStream_t st, const char* path, const void* hdr, size_t hdr_bytes, const DevBuf& buf, uint64_t count) {
+  HIPCHK(hipStreamSynchronize(st));
+  std::vector<uint64_t> t(count);
+  HIPCHK(hipMemcpy(t.data(), buf.p, count * 8, hipMemcpyDeviceToHost));
+  static std::mutex mu;   // the teams' launching workers share the file
+  std::lock_guard<std::mutex> lk(mu);
+  if (FILE* f = fopen(path, "ab")) {
+    fwrite(hdr, 1, hdr_bytes, f);
+    fwrite(t.data(), 8, count, f);
+    fclose(f);
+  }
+  return 0;
+}
+#endif
+
+// ---------------------------------------------------------------------------
 // PianoPIR engine: P partitions (P = 1 for PianoPIR, BatchSize/2 for the batch)
 // ---------------------------------------------------------------------------
 struct PartHost {
@@ -466,14 +543,15 @@ struct Engine {
   uint32_t gran_words = 0;
   std::vector<uint32_t> owned_list;   // owned partitions in order (owned_d holds their PmPart)
   DevBuf qoffs, ans_srv;
-  DevBuf subs_d, sb_d, bits, cand, meta, spec, res_d, ans, part_x, qvec, stamps, helpg;
+  StepBufs buf;   // the step's scratch (engine_step)
+  DevBuf helpg;   // k_step's gather helpers' hand-off granules
   std::vector<double> stamp_sum;   // PM_STAMPS builds: accumulated phase deltas
   uint64_t stamp_n = 0;
   uint32_t step_token = 0;         // PmStep::token of the last step
   uint64_t step_seq = 0;           // its completion sequence number (pm_ctx::record_done)
   size_t pf_off = 0, pf_len = ~size_t(0);   // bytes of each result row the caller reads next
   bool rows_partial = false;   // this call's caller reads ONLY those bytes (GetVertexInfo): the rest is not sent
-  HostBuf desc_h, out_h, err_h, src_h;   // src_h: pm_batchpir_query_dev's row pointers
+  HostBuf err_h, src_h;   // src_h: pm_batchpir_query_dev's row pointers
   HostBuf stage_h;                       // ... and its rows of a multi-step query (pinned staging)
   hipEvent_t dev_ev = nullptr;           // ... its completion, for the consumer's stream
   ~Engine() {
@@ -1137,7 +1215,7 @@ static void post_results(Engine* g, PmOutHdr* hdr, uint64_t* rows, uint32_t nsub
 #ifdef PM_STAMPS
   {   // partition 0's phase deltas in shader clocks, accumulated; printed at exit
     std::vector<uint64_t> t(64);
-    (void)hipMemcpy(t.data(), g->stamps.p, 64 * 8, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(t.data(), g->buf.stamps.p, 64 * 8, hipMemcpyDeviceToHost);
     g->stamp_sum.resize(64, 0.0);
     for (int i = 1; i < 64; ++i)
     {   // each kernel's stamps relative to its own first one
@@ -1156,32 +1234,20 @@ static int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
   const uint32_t nsub = (uint32_t)g->subs.size();
   if (nsub == 0) return 0;
   const uint64_t E = g->E;
-  const uint32_t words = (g->maxPH + 63) / 64;
-  CHK(g->subs_d.reserve(nsub * sizeof(PmSub)));
-  CHK(g->sb_d.reserve((g->P + 1) * 4));
-  CHK(g->bits.reserve((uint64_t)nsub * words * 8));
-  const uint32_t cblk = pmk::step_match_blocks(g->maxPH);
-  CHK(g->cand.reserve((uint64_t)nsub * cblk * 6 * 4));
-  CHK(g->meta.reserve((uint64_t)nsub * 2 * 4));
-  CHK(g->spec.reserve((uint64_t)nsub * 64 * 4));
-  CHK(g->res_d.reserve(nsub * sizeof(PmRes)));
-  CHK(g->ans.reserve((uint64_t)nsub * E * 8));
+  const uint32_t words = (g->maxPH + 63) / 64, cblk = pmk::step_match_blocks(g->maxPH);
+  StepBufs& B = g->buf;
+  CHK(B.reserve(nsub, (uint32_t)g->P, words, cblk, E));
   const size_t dsub = nsub * sizeof(PmSub);
-  CHK(g->desc_h.reserve(dsub + (g->P + 1) * 4));
-  CHK(g->out_h.reserve(nsub * sizeof(PmOutHdr) + (size_t)nsub * E * 8));
-  char* dh = g->desc_h.as<char>();
+  CHK(B.desc_h.reserve(dsub + (g->P + 1) * 4));
+  CHK(B.out_h.reserve(step_out_bytes(nsub, E)));
+  char* dh = B.desc_h.as<char>();
   memcpy(dh, g->subs.data(), dsub);
   memcpy(dh + dsub, g->sb.data(), (g->P + 1) * 4);
   PmStep S{};
   S.parts = g->parts_d.as<PmPart>();
   S.subs_h = (const PmSub*)dh;
   S.sb_h = (const uint32_t*)(dh + dsub);
-  S.subs = g->subs_d.as<PmSub>();
-  S.sb = g->sb_d.as<uint32_t>();
-  S.bits = g->bits.as<uint64_t>();
-  S.cand = g->cand.as<uint32_t>();
-  S.meta = g->meta.as<uint32_t>();
-  S.spec = g->spec.as<uint32_t>();
+  B.fill(S, words, cblk);
   if (words <= g->gran_words) {   // k_step granules (sized at creation for maxPH)
     uint64_t* gb = g->gran.as<uint64_t>();
     S.recg = gb;
@@ -1190,30 +1256,20 @@ static int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
     S.resg = gb + kArgSubs * (8 + 64 + 2 * (uint64_t)g->gran_words);
     S.err_h = g->err_h.as<uint32_t>();
   }
-  S.cblk = cblk;
-  S.res = g->res_d.as<PmRes>();
-  S.ans = g->ans.as<uint64_t>();
   S.done = g->done.as<uint32_t>();
 #ifdef PM_STAMPS
-  CHK(g->stamps.reserve(g->P * 64 * 8));
-  HIPCHK(hipMemsetAsync(g->stamps.p, 0, g->P * 64 * 8, st));
-  S.stamps = g->stamps.as<uint64_t>();
+  CHK(B.stamps.reserve(g->P * 64 * 8));
+  HIPCHK(hipMemsetAsync(B.stamps.p, 0, g->P * 64 * 8, st));
+  S.stamps = B.stamps.as<uint64_t>();
 #endif
   S.db = g->db->as<uint64_t>();
   S.q = q_dev;
-  S.hdr_h = g->out_h.as<PmOutHdr>();
-  S.rows_h = (uint64_t*)(g->out_h.as<char>() + nsub * sizeof(PmOutHdr));
-  S.words = words; S.E = (uint32_t)E; S.dim = q_dev ? dim : 0; S.nsub = nsub; S.np = (uint32_t)g->P;
+  step_out(S, B.out_h.p, nsub);
+  S.E = (uint32_t)E; S.dim = q_dev ? dim : 0; S.nsub = nsub; S.np = (uint32_t)g->P;
   S.args_valid = (nsub <= kArgSubs && g->P <= kArgParts) ? 1u : 0u;
-  if (++g->step_token == 0) ++g->step_token;   // 0 never marks a published header
-  S.token = g->step_token;
-  {   // row words the consumer reads: checksummed in the header (PmOutHdr)
-    const size_t off = std::min<size_t>(g->pf_off, E * 8);
-    const size_t end = std::min<size_t>(E * 8, off + std::min<size_t>(g->pf_len, E * 8));
-    S.pf_w0 = (uint32_t)(off / 8);
-    S.pf_w1 = (uint32_t)((end + 7) / 8);
-    S.rows_partial = g->rows_partial && !c->verify_rows && !c->debug_cache ? 1u : 0u;
-  }
+  S.token = next_token(g->step_token);
+  step_read_window(S, g->pf_off, g->pf_len, E);
+  S.rows_partial = host_rows_partial(c, g->rows_partial);
   if (S.args_valid) {
     memcpy(S.subs_a, g->subs.data(), dsub);
     memcpy(S.sb_a, g->sb.data(), (g->P + 1) * 4);
@@ -1251,9 +1307,9 @@ static int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
     S.helpg = g->helpg.as<uint64_t>();
 #ifdef PM_STEP_STAMPS
     const uint32_t grid = 2 * nsub + (uint32_t)g->P + S.nhelp * nsub;
-    CHK(g->stamps.reserve((uint64_t)grid * 8 * 8));
-    HIPCHK(hipMemsetAsync(g->stamps.p, 0, (uint64_t)grid * 8 * 8, st));
-    S.stamps = g->stamps.as<uint64_t>();
+    CHK(B.stamps.reserve((uint64_t)grid * 8 * 8));
+    HIPCHK(hipMemsetAsync(B.stamps.p, 0, (uint64_t)grid * 8 * 8, st));
+    S.stamps = B.stamps.as<uint64_t>();
 #endif
     c->timed_ext("step", ans_bytes, [&](pmk::PmEvents ev) { pmk::step_fused(st, S, ev); }, 2);
     g->step_seq = c->record_done(st);
@@ -1266,15 +1322,8 @@ static int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
     }
 #ifdef PM_STEP_STAMPS
     if (const char* fn = getenv("PM_STAMP_FILE")) {   // append {grid, nsub, cblk, np} + grid x 8 stamps
-      HIPCHK(hipStreamSynchronize(st));
-      std::vector<uint64_t> t((uint64_t)grid * 8);
-      HIPCHK(hipMemcpy(t.data(), g->stamps.p, t.size() * 8, hipMemcpyDeviceToHost));
-      if (FILE* f = fopen(fn, "ab")) {
-        const uint32_t h[4] = {grid, nsub, cblk, (uint32_t)g->P};
-        fwrite(h, 4, 4, f);
-        fwrite(t.data(), 8, t.size(), f);
-        fclose(f);
-      }
+      const uint32_t h[4] = {grid, nsub, cblk, (uint32_t)g->P};
+      CHK(dump_stamps(st, fn, h, sizeof h, B.stamps, (uint64_t)grid * 8));
     }
 #endif
     return 0;
@@ -1301,8 +1350,8 @@ static int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
   }
   S.nsplit = c->no_split ? 1 : pmk::step_gather_split(g->maxSS, nsub);
   if (S.nsplit > 1) {
-    CHK(g->part_x.reserve((uint64_t)nsub * S.nsplit * (E & ~3ull) * 8));
-    S.part_x = g->part_x.as<uint64_t>();
+    CHK(B.part_x.reserve((uint64_t)nsub * S.nsplit * (E & ~3ull) * 8));
+    S.part_x = B.part_x.as<uint64_t>();
     c->timed_ext("gather", ans_bytes, [&](pmk::PmEvents ev) { pmk::step_gather(st, S, ev); }, 2);
   }
   c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { pmk::step_answer(st, S, g->maxSS, ev); }, 2);
@@ -2584,8 +2633,11 @@ struct StepGroup {
   std::vector<uint32_t> lp;
   uint32_t Pl = 0;
   bool ph8 = false;
-  DevBuf parts_d, subs_d, sb_d, bits, cand, meta, spec, res_d, ans, part_x, done, prep_parts, desc_d, stamps, qset;
-  HostBuf desc_h, out_h;
+  // the shared step's scratch (group_step).  The device loop sizes it once
+  // (drl_team_init) and its kernels keep the pointers: no group_step, nor any
+  // other reserve of it, on a DrlTeam's group after that
+  StepBufs buf;
+  DevBuf parts_d, done, prep_parts, desc_d, qset;
   uint32_t token = 0, pf_w0 = 0, pf_w1 = 0;
   uint64_t seq = 0;   // the last shared step's completion sequence number (pm_ctx::record_done)
   std::vector<PmSub> subs;
@@ -2724,8 +2776,8 @@ static void group_stage_session(StepGroup& G, uint32_t s) {
 static int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uint32_t nreal, double ans_bytes) {
   pm_ctx* c = G.c;
   hipStream_t st = c->stream;
-  const uint32_t nsub = S.nsub, np = S.np;
-  (void)np;
+  const uint32_t nsub = S.nsub;
+  StepBufs& B = G.buf;
   auto t0 = Clock::now();
   const bool lds = pmk::step_resolve_lds_ok(G.maxPH, max_per_part);
   S.nsplit = c->no_split ? 1 : pmk::step_gather_split(G.maxSS, nsub);
@@ -2741,26 +2793,17 @@ static int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uin
     static const char* mr_file = getenv("PM_MR_STAMPS");   // append {np} + np x 8 stamps per step
     static std::atomic<int> mr_steps{0};   // the first 40 steps of the run
     const bool mr_this = mr_file && mr_steps.fetch_add(1) < 40;
+    const uint64_t np = S.np;
     if (mr_this) {
-      CHK(G.stamps.reserve((uint64_t)np * 8 * 8));
-      HIPCHK(hipMemsetAsync(G.stamps.p, 0, (uint64_t)np * 8 * 8, st));
-      S.stamps = G.stamps.as<uint64_t>();
+      CHK(B.stamps.reserve(np * 8 * 8));
+      HIPCHK(hipMemsetAsync(B.stamps.p, 0, np * 8 * 8, st));
+      S.stamps = B.stamps.as<uint64_t>();
     }
 #endif
     c->timed_ext("match_resolve", (double)nreal * G.maxPH, [&](pmk::PmEvents ev) { pmk::step_match_resolve(st, S, opts, G.ph8, G.maxPH, max_per_part, ev); }, 2);
 #ifdef PM_MR_STAMPS
     if (mr_this) {
-      HIPCHK(hipStreamSynchronize(st));
-      std::vector<uint64_t> t((uint64_t)np * 8);
-      HIPCHK(hipMemcpy(t.data(), G.stamps.p, t.size() * 8, hipMemcpyDeviceToHost));
-      static std::mutex mu;
-      std::lock_guard<std::mutex> lk(mu);
-      if (FILE* f = fopen(mr_file, "ab")) {
-        const uint64_t h = np;
-        fwrite(&h, 8, 1, f);
-        fwrite(t.data(), 8, t.size(), f);
-        fclose(f);
-      }
+      CHK(dump_stamps(st, mr_file, &np, sizeof np, B.stamps, np * 8));
       S.stamps = nullptr;
     }
 #endif
@@ -2771,8 +2814,8 @@ static int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uin
     c->timed_ext("resolve", 0, [&](pmk::PmEvents ev) { pmk::step_resolve(st, S, lds, ev); }, 2);
   }
   if (S.nsplit > 1) {
-    CHK(G.part_x.reserve((uint64_t)nsub * S.nsplit * (G.E & ~3u) * 8));
-    S.part_x = G.part_x.as<uint64_t>();
+    CHK(B.part_x.reserve((uint64_t)nsub * S.nsplit * (G.E & ~3u) * 8));
+    S.part_x = B.part_x.as<uint64_t>();
     c->timed_ext("gather", ans_bytes, [&](pmk::PmEvents ev) { pmk::step_gather(st, S, ev); }, 2);
   }
 #ifdef PM_ANSWER_STAMPS
@@ -2780,9 +2823,9 @@ static int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uin
   static std::atomic<int> stamp_steps{0};   // the first 40 steps of the run (file size)
   const bool stamp_this = stamp_file && stamp_steps.fetch_add(1) < 40;
   if (stamp_this) {
-    CHK(G.stamps.reserve((uint64_t)nsub * 8 * 8));
-    HIPCHK(hipMemsetAsync(G.stamps.p, 0, (uint64_t)nsub * 8 * 8, st));
-    S.stamps = G.stamps.as<uint64_t>();
+    CHK(B.stamps.reserve((uint64_t)nsub * 8 * 8));
+    HIPCHK(hipMemsetAsync(B.stamps.p, 0, (uint64_t)nsub * 8 * 8, st));
+    S.stamps = B.stamps.as<uint64_t>();
   }
 #endif
   c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { pmk::step_answer(st, S, G.maxSS, ev); }, 2);
@@ -2790,17 +2833,8 @@ static int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uin
   HIPCHK(hipGetLastError());
 #ifdef PM_ANSWER_STAMPS
   if (stamp_this) {
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<uint64_t> t((uint64_t)nsub * 8);
-    HIPCHK(hipMemcpy(t.data(), G.stamps.p, t.size() * 8, hipMemcpyDeviceToHost));
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    if (FILE* f = fopen(stamp_file, "ab")) {
-      const uint64_t h = nsub;
-      fwrite(&h, 8, 1, f);
-      fwrite(t.data(), 8, t.size(), f);
-      fclose(f);
-    }
+    const uint64_t h = nsub;
+    CHK(dump_stamps(st, stamp_file, &h, sizeof h, B.stamps, (uint64_t)nsub * 8));
   }
 #endif
   c->host_add(HT_STEP_LAUNCH, ms_since(t0));
@@ -2888,23 +2922,16 @@ static int group_step(StepGroup& G, const std::vector<char>& in) {
   }
   if (nsub == 0) return 0;
   const uint32_t words = (G.maxPH + 63) / 64, cblk = pmk::step_match_blocks(G.maxPH);
-  CHK(G.subs_d.reserve(nsub * sizeof(PmSub)));
-  CHK(G.sb_d.reserve((np + 1) * 4));
-  CHK(G.bits.reserve((uint64_t)nsub * words * 8));
-  CHK(G.cand.reserve((uint64_t)nsub * cblk * 6 * 4));
-  CHK(G.meta.reserve((uint64_t)nsub * 2 * 4));
-  CHK(G.spec.reserve((uint64_t)nsub * 64 * 4));
-  CHK(G.res_d.reserve(nsub * sizeof(PmRes)));
-  CHK(G.ans.reserve((uint64_t)nsub * G.E * 8));
+  StepBufs& B = G.buf;
+  CHK(B.reserve(nsub, np, words, cblk, G.E));
   const size_t dsub = nsub * sizeof(PmSub);
-  if (!G.comb) CHK(G.out_h.reserve(nsub * sizeof(PmOutHdr) + (size_t)nsub * G.E * 8));
   char* dh;
   if (staged) {   // the compacted slots are the descriptor; the offsets right after them
     dh = G.stage_h.as<char>();
     memcpy(dh + dsub, G.sb.data(), (np + 1) * 4);
   } else {
-    CHK(G.desc_h.reserve(dsub + (np + 1) * 4));
-    dh = G.desc_h.as<char>();
+    CHK(B.desc_h.reserve(dsub + (np + 1) * 4));
+    dh = B.desc_h.as<char>();
     memcpy(dh, G.subs.data(), dsub);
     memcpy(dh + dsub, G.sb.data(), (np + 1) * 4);
   }
@@ -2912,6 +2939,7 @@ static int group_step(StepGroup& G, const std::vector<char>& in) {
   S.parts = G.parts_d.as<PmPart>();
   S.subs_h = (const PmSub*)dh;
   S.sb_h = (const uint32_t*)(dh + dsub);
+  B.fill(S, words, cblk);
   if (!(nsub <= kArgSubs && np <= kArgParts)) {
     // a large descriptor crosses PCIe once, by DMA, instead of as thousands of
     // zero-copy reads by the match workgroups; k_match* stage it from here
@@ -2919,48 +2947,30 @@ static int group_step(StepGroup& G, const std::vector<char>& in) {
     HIPCHK(hipMemcpyAsync(G.desc_d.p, dh, dsub + (np + 1) * 4, hipMemcpyHostToDevice, st));
     S.subs_h = G.desc_d.as<PmSub>();
     S.sb_h = (const uint32_t*)(G.desc_d.as<char>() + dsub);
-  }
-  S.subs = G.subs_d.as<PmSub>();
-  S.sb = G.sb_d.as<uint32_t>();
-  if (!(nsub <= kArgSubs && np <= kArgParts)) {   // the DMA'd descriptor is the device copy
-    S.subs = const_cast<PmSub*>(S.subs_h);
+    S.subs = const_cast<PmSub*>(S.subs_h);   // the DMA'd descriptor is the device copy
     S.sb = const_cast<uint32_t*>(S.sb_h);
   }
-  S.bits = G.bits.as<uint64_t>();
-  S.cand = G.cand.as<uint32_t>();
-  S.meta = G.meta.as<uint32_t>();
-  S.spec = G.spec.as<uint32_t>();
-  S.cblk = cblk;
-  S.res = G.res_d.as<PmRes>();
-  S.ans = G.ans.as<uint64_t>();
   S.done = G.done.as<uint32_t>();
   Engine* e0 = G.es[0];
   S.db = e0->db->as<uint64_t>();
   S.q = nullptr;   // each partition's PmPart::qv
   if (G.comb) {   // sharded: results stay on the device for group_exchange's records
-    CHK(G.out_d.reserve(nsub * sizeof(PmOutHdr) + (size_t)nsub * G.E * 8));
-    S.hdr_h = G.out_d.as<PmOutHdr>();
-    S.rows_h = (uint64_t*)(G.out_d.as<char>() + nsub * sizeof(PmOutHdr));
+    CHK(G.out_d.reserve(step_out_bytes(nsub, G.E)));
+    step_out(S, G.out_d.p, nsub);
   } else {
-    S.hdr_h = G.out_h.as<PmOutHdr>();
-    S.rows_h = (uint64_t*)(G.out_h.as<char>() + nsub * sizeof(PmOutHdr));
+    CHK(B.out_h.reserve(step_out_bytes(nsub, G.E)));
+    step_out(S, B.out_h.p, nsub);
   }
-  S.words = words; S.E = G.E; S.dim = G.dim; S.nsub = nsub; S.np = np;
+  S.E = G.E; S.dim = G.dim; S.nsub = nsub; S.np = np;
   S.np_live = np_live;
   S.args_valid = (nsub <= kArgSubs && np <= kArgParts) ? 1u : 0u;
   if (S.args_valid) {   // (never the staged form)
     memcpy(S.subs_a, G.subs.data(), dsub);
     memcpy(S.sb_a, G.sb.data(), (np + 1) * 4);
   }
-  if (++G.token == 0) ++G.token;
-  S.token = G.token;
-  {
-    const size_t off = std::min<size_t>(e0->pf_off, G.E * 8);
-    const size_t end = std::min<size_t>(G.E * 8, off + std::min<size_t>(e0->pf_len, G.E * 8));
-    S.pf_w0 = (uint32_t)(off / 8);
-    S.pf_w1 = (uint32_t)((end + 7) / 8);
-    S.rows_partial = G.rows_partial && !c->verify_rows && !c->debug_cache ? 1u : 0u;
-  }
+  S.token = next_token(G.token);
+  step_read_window(S, e0->pf_off, e0->pf_len, G.E);
+  S.rows_partial = host_rows_partial(c, G.rows_partial);
   return group_step_launch(G, S, max_per_part, nreal, ans_bytes);
 }
 
@@ -2971,8 +2981,8 @@ static int group_step(StepGroup& G, const std::vector<char>& in) {
 static void prefetch_session(StepGroup& G, uint32_t s, const pm_graph* g) {
   const Engine* e = G.es[s];
   const uint32_t n = (uint32_t)e->subs.size();
-  const PmOutHdr* hdr = G.out_h.as<PmOutHdr>() + G.base[s];
-  const char* rows = G.out_h.as<char>() + (size_t)G.nsub * sizeof(PmOutHdr) + (size_t)G.base[s] * G.E * 8;
+  const PmOutHdr* hdr = G.buf.out_h.as<PmOutHdr>() + G.base[s];
+  const char* rows = G.buf.out_h.as<char>() + (size_t)G.nsub * sizeof(PmOutHdr) + (size_t)G.base[s] * G.E * 8;
   for (uint32_t j = 0; j < n; j += 2) __builtin_prefetch(hdr + j);
   for (uint32_t j = 0; j < n; ++j)
     for (uint32_t w = G.pf_w0; w < G.pf_w1; w += 8) __builtin_prefetch(rows + ((size_t)j * G.E + w) * 8);
@@ -2990,8 +3000,8 @@ static int group_collect(StepGroup& G, uint32_t s) {
   const uint32_t n = (uint32_t)e->subs.size();
   for (uint32_t j = 0; j < n; ++j)   // the localCache slots post_results fills, requested ahead
     if (e->subs[j].kind == SUB_REAL) e->parts[e->subs[j].part].cache.prefetch(e->subs[j].idx);
-  PmOutHdr* hdr = G.out_h.as<PmOutHdr>();
-  uint64_t* rows = (uint64_t*)(G.out_h.as<char>() + (size_t)G.nsub * sizeof(PmOutHdr));
+  PmOutHdr* hdr = G.buf.out_h.as<PmOutHdr>();
+  uint64_t* rows = (uint64_t*)(G.buf.out_h.as<char>() + (size_t)G.nsub * sizeof(PmOutHdr));
   auto t_wait = Clock::now();
   CHK(wait_step(e->ctx, hdr + G.base[s], n, G.token, (const char*)(rows + (uint64_t)G.base[s] * G.E),
                 (size_t)G.E * 8, (size_t)G.pf_w0 * 8, (size_t)(G.pf_w1 - G.pf_w0) * 8, G.seq, G.c));
@@ -4096,8 +4106,8 @@ struct DrlTeam {
   StepGroup G;
   pm_graph** gs = nullptr;
   uint32_t S = 0, s0 = 0, nsub = 0;
-  DevBuf sess, dummy, batch, heap, ktab, knb, kdist, kid, ctabp, answers, subs, gid, sb, out, allq, part_bytes,
-      step_bytes, step_real, stamps;
+  DevBuf sess, dummy, batch, heap, ktab, knb, kdist, kid, ctabp, answers, gid, out, allq, part_bytes, step_bytes,
+      step_real, stamps;
   DrlArgs A{};
   hipEvent_t ev_end = nullptr;
   HostBuf prep_stage, parts_stage;               // pinned stages of the asynchronous maintenance (run_batched_dev)
@@ -4158,10 +4168,11 @@ static int drl_team_init(DrlTeam& T, pm_graph** gs, uint32_t S, uint32_t s0, con
   CHK(T.kid.reserve((uint64_t)S * kcap * 4));
   CHK(T.ctabp.reserve(S * 8));
   CHK(T.answers.reserve(std::max<uint64_t>(8, (uint64_t)S * q * k * 8)));
-  CHK(T.subs.reserve((uint64_t)T.nsub * sizeof(PmSub)));
+  // the step buffers of group_step for nsub sub-queries; the descriptor in them
+  // (subs_d, sb_d) is the one the round kernels build
+  CHK(G.buf.reserve(T.nsub, S * P, (G.maxPH + 63) / 64, pmk::step_match_blocks(G.maxPH), G.E));
   CHK(T.gid.reserve((uint64_t)T.nsub * 8));
-  CHK(T.sb.reserve((uint64_t)(S * P + 1) * 4));
-  CHK(T.out.reserve((uint64_t)T.nsub * sizeof(PmOutHdr) + (uint64_t)T.nsub * G.E * 8));
+  CHK(T.out.reserve(step_out_bytes(T.nsub, G.E)));
   CHK(T.allq.reserve(std::max<uint64_t>(4, (uint64_t)S * q * dim * 4)));
   CHK(T.part_bytes.reserve(P * 8));
   // host state -> device: search streams and counters, dummy counters, localCache indexes
@@ -4183,7 +4194,7 @@ static int drl_team_init(DrlTeam& T, pm_graph** gs, uint32_t S, uint32_t s0, con
   HIPCHK(hipMemcpy(T.sess.p, hs.data(), S * sizeof(DrlSess), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(T.dummy.p, dmy.data(), dmy.size() * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(T.ctabp.p, ctp.data(), S * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(T.sb.p, sbv.data(), sbv.size() * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(G.buf.sb_d.p, sbv.data(), sbv.size() * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(T.part_bytes.p, pb.data(), P * 8, hipMemcpyHostToDevice));
   if (q) HIPCHK(hipMemcpy(T.allq.p, queries + (uint64_t)s0 * q * dim, (uint64_t)S * q * dim * 4, hipMemcpyHostToDevice));
   if (G.c->timing >= 2) {   // each step's answer bytes and real sub-queries, counted by the round that builds it
@@ -4198,14 +4209,6 @@ static int drl_team_init(DrlTeam& T, pm_graph** gs, uint32_t S, uint32_t s0, con
     CHK(T.stamps.reserve(16 * 8));
     HIPCHK(hipMemset(T.stamps.p, 0, 16 * 8));
   }
-  // the step buffers of group_step for nsub sub-queries
-  const uint32_t words = (G.maxPH + 63) / 64, cblk = pmk::step_match_blocks(G.maxPH);
-  CHK(G.bits.reserve((uint64_t)T.nsub * words * 8));
-  CHK(G.cand.reserve((uint64_t)T.nsub * cblk * 6 * 4));
-  CHK(G.meta.reserve((uint64_t)T.nsub * 2 * 4));
-  CHK(G.spec.reserve((uint64_t)T.nsub * 64 * 4));
-  CHK(G.res_d.reserve(T.nsub * sizeof(PmRes)));
-  CHK(G.ans.reserve((uint64_t)T.nsub * G.E * 8));
   DrlArgs& A = T.A;
   A.S = S; A.P = P; A.qn = sh.qn; A.n = n; A.m = m; A.parallel = (uint32_t)parallel; A.k = (uint32_t)k;
   A.E = G.E; A.dim = dim; A.kcap = kcap; A.cmask = sh.cmask; A.ns = G.ns; A.q = (uint32_t)q;
@@ -4213,7 +4216,7 @@ static int drl_team_init(DrlTeam& T, pm_graph** gs, uint32_t S, uint32_t s0, con
   A.vec16 = (G.E % 2 == 0 && dim % 4 == 0 && m % 4 == 0 && ((m / 4) & (m / 4 - 1)) == 0) ? 1u : 0u;
   A.hdr = T.out.as<PmOutHdr>();
   A.rows = (const uint64_t*)(T.out.as<char>() + (uint64_t)T.nsub * sizeof(PmOutHdr));
-  A.subs = T.subs.as<PmSub>(); A.gid = T.gid.as<uint64_t>();
+  A.subs = G.buf.subs_d.as<PmSub>(); A.gid = T.gid.as<uint64_t>();
   A.graph = g0->dgraph->as<uint32_t>();
   A.start_dist = G.start_dist.as<float>(); A.start_ids = G.start_ids.as<uint32_t>();
   A.sess = T.sess.as<DrlSess>(); A.dummy = T.dummy.as<uint64_t>(); A.batch = T.batch.as<uint32_t>();
@@ -4237,25 +4240,19 @@ static int drl_step(DrlTeam& T, const DrlShape& sh) {
   c->sample_now = c->sample_ctr++ % 7 == 0;   // timing level 3: group_step's sample
   PmStep S{};
   S.parts = G.parts_d.as<PmPart>();
-  S.subs_h = S.subs = T.subs.as<PmSub>();
-  S.sb_h = S.sb = T.sb.as<uint32_t>();
-  S.bits = G.bits.as<uint64_t>(); S.cand = G.cand.as<uint32_t>(); S.meta = G.meta.as<uint32_t>();
-  S.spec = G.spec.as<uint32_t>(); S.cblk = pmk::step_match_blocks(G.maxPH);
-  S.res = G.res_d.as<PmRes>(); S.ans = G.ans.as<uint64_t>(); S.done = G.done.as<uint32_t>();
+  G.buf.fill(S, (G.maxPH + 63) / 64, pmk::step_match_blocks(G.maxPH));
+  S.subs_h = S.subs;   // the descriptor is on the device already
+  S.sb_h = S.sb;
+  S.done = G.done.as<uint32_t>();
   S.db = e0->db->as<uint64_t>();
   S.q = nullptr;   // each partition's PmPart::qv
-  S.hdr_h = T.out.as<PmOutHdr>();
-  S.rows_h = (uint64_t*)(T.out.as<char>() + (uint64_t)T.nsub * sizeof(PmOutHdr));
-  S.words = (G.maxPH + 63) / 64; S.E = G.E; S.dim = G.dim; S.nsub = T.nsub; S.np = T.S * G.Pl;
+  step_out(S, T.out.p, T.nsub);
+  S.E = G.E; S.dim = G.dim; S.nsub = T.nsub; S.np = T.S * G.Pl;
   S.np_live = S.np;
   S.args_valid = 0;
-  if (++G.token == 0) ++G.token;
-  S.token = G.token;
-  const size_t off = std::min<size_t>(e0->pf_off, G.E * 8);
-  const size_t end = std::min<size_t>(G.E * 8, off + std::min<size_t>(e0->pf_len, G.E * 8));
-  S.pf_w0 = (uint32_t)(off / 8);
-  S.pf_w1 = (uint32_t)((end + 7) / 8);
-  S.rows_partial = 1;
+  S.token = next_token(G.token);
+  step_read_window(S, e0->pf_off, e0->pf_len, G.E);
+  S.rows_partial = 1;   // the rows stay on the device: no host diagnostic re-reads them
   const size_t before = c->launches.size();
   // bytes: every sub-query answered (patched with the round's exact count in timing runs)
   double ans_bytes = 0;
@@ -4497,39 +4494,27 @@ extern "C" int pm_search_loop_batched(pm_graph** gs, uint32_t S, const float* qu
   DrlShape sh;
   if (drl_plan(gs, S, q, k, step, parallel, &sh)) {   // every round on the GPU (run_batched_dev)
     CHK(run_batched_dev(gs, S, queries, q, k, step, parallel, NG, answers, mt.data(), sh));
-    const double wall = std::chrono::duration<double>(Clock::now() - t0).count();
-    if (wall_s) *wall_s = wall;
-    for (uint32_t s = 0; s < S; ++s) {
-      if (online_s) online_s[s] = wall - mt[s];
-      if (maint_s) maint_s[s] = mt[s];
+  } else {
+    static const int pool = [] { const char* e = getenv("PM_BATCH_POOL"); return e ? atoi(e) : 1; }();
+    if (pool && NG > 1) {   // the pooled workers (run_batched_pool); one team: the workers serve it alone anyway
+      CHK(run_batched_pool(gs, S, queries, q, k, step, parallel, NG, TT, answers, mt.data()));
+    } else {
+      for (uint32_t g = 0; g < NG; ++g) {
+        const uint32_t s0 = (uint32_t)((uint64_t)S * g / NG), s1 = (uint32_t)((uint64_t)S * (g + 1) / NG);
+        const uint32_t Tg = std::max(1u, std::min(s1 - s0, (uint32_t)((uint64_t)TT * (g + 1) / NG - (uint64_t)TT * g / NG)));
+        teams.emplace_back([&, g, s0, s1, Tg] {
+          if (hipSetDevice(gs[0]->ctx->device) != hipSuccess) { rc[g] = PM_EHIP; msg[g] = "hipSetDevice"; return; }
+          rc[g] = run_batched_team(gs + s0, s1 - s0, qbase + (uint64_t)s0 * q * gs[0]->dim, q, k, step, parallel, Tg,
+                                   answers + (uint64_t)s0 * q * (uint64_t)k, mt.data() + s0);
+          if (rc[g]) msg[g] = pm_last_error();
+        });
+      }
+      for (auto& t : teams) t.join();
+      for (uint32_t g = 0; g < NG; ++g)
+        if (rc[g]) return fail(rc[g], "group " + std::to_string(g) + ": " + msg[g]);
     }
-    return 0;
   }
-  static const int pool = [] { const char* e = getenv("PM_BATCH_POOL"); return e ? atoi(e) : 1; }();
-  if (pool && NG > 1) {   // the pooled workers (run_batched_pool); one team: the workers serve it alone anyway
-    CHK(run_batched_pool(gs, S, queries, q, k, step, parallel, NG, TT, answers, mt.data()));
-    const double wall = std::chrono::duration<double>(Clock::now() - t0).count();
-    if (wall_s) *wall_s = wall;
-    for (uint32_t s = 0; s < S; ++s) {
-      if (online_s) online_s[s] = wall - mt[s];
-      if (maint_s) maint_s[s] = mt[s];
-    }
-    return 0;
-  }
-  for (uint32_t g = 0; g < NG; ++g) {
-    const uint32_t s0 = (uint32_t)((uint64_t)S * g / NG), s1 = (uint32_t)((uint64_t)S * (g + 1) / NG);
-    const uint32_t Tg = std::max(1u, std::min(s1 - s0, (uint32_t)((uint64_t)TT * (g + 1) / NG - (uint64_t)TT * g / NG)));
-    teams.emplace_back([&, g, s0, s1, Tg] {
-      if (hipSetDevice(gs[0]->ctx->device) != hipSuccess) { rc[g] = PM_EHIP; msg[g] = "hipSetDevice"; return; }
-      rc[g] = run_batched_team(gs + s0, s1 - s0, qbase + (uint64_t)s0 * q * gs[0]->dim, q, k, step, parallel, Tg,
-                               answers + (uint64_t)s0 * q * (uint64_t)k, mt.data() + s0);
-      if (rc[g]) msg[g] = pm_last_error();
-    });
-  }
-  for (auto& t : teams) t.join();
   const double wall = std::chrono::duration<double>(Clock::now() - t0).count();
-  for (uint32_t g = 0; g < NG; ++g)
-    if (rc[g]) return fail(rc[g], "group " + std::to_string(g) + ": " + msg[g]);
   if (wall_s) *wall_s = wall;
   for (uint32_t s = 0; s < S; ++s) {
     if (online_s) online_s[s] = wall - mt[s];
