@@ -252,6 +252,21 @@ int  pm_graph_preprocess(pm_graph* g);   /* GraphANNFrontend.Preprocess  search.
 /* GraphANNFrontend.SearchKNN (search.go:114-234); ids/steps: k entries, -1 padded */
 int  pm_search_knn(pm_graph* g, const float* query, int k, int max_step, int parallel,
                    int benchmarking, int64_t* ids, int64_t* steps);
+/* GraphANNFrontend.SearchKNNBatch (graphann/search.go:236-245): SearchKNN of
+ * queries[i] for i = 0..nq-1 in order; ids/steps: nq x k, -1 padded.  The
+ * result (ids, steps, pm_graph_counts, the id stream afterwards) is that of
+ * the loop of pm_search_knn, for every graph and argument it accepts.  A
+ * non-private in-memory graph is searched on the device, one workgroup per
+ * query and all queries of a call in one launch ("knn_batch" at timing level
+ * 1), when the search state fits the LDS (m <= 64, parallel * m <= 256, about
+ * 36 B x parallel x (1 + max_step x m) rounded up to a power of two, within
+ * 160 KB) and benchmarking is 0; a query whose search would draw from the id
+ * stream (a pop on an empty heap) is re-run on the host in order
+ * ("host_knn_batch_fallback").  *device_queries (nullable): the number of
+ * queries answered by the kernel, 0 on the sequential path. */
+int  pm_search_knn_batch(pm_graph* g, const float* queries, uint64_t nq, int k, int max_step,
+                         int parallel, int benchmarking, int64_t* ids, int64_t* steps,
+                         uint64_t* device_queries);
 /* private-search.go:216-240 query loop incl. the maintenance trigger (:226-232) */
 int  pm_search_loop(pm_graph* g, const float* queries, uint64_t q, int k, int step, int parallel,
                     int benchmarking, int64_t* answers, double* online_s, double* maintenance_s);

@@ -106,6 +106,7 @@ SIGNATURES = {
     "pm_graph_destroy": (None, [vp]),
     "pm_graph_preprocess": (C.c_int, [vp]),
     "pm_search_knn": (C.c_int, [vp, f32p, C.c_int, C.c_int, C.c_int, C.c_int, i64p, i64p]),
+    "pm_search_knn_batch": (C.c_int, [vp, f32p, u64, C.c_int, C.c_int, C.c_int, C.c_int, i64p, i64p, u64p]),
     "pm_search_loop": (C.c_int, [vp, f32p, u64, C.c_int, C.c_int, C.c_int, C.c_int, i64p,
                                  C.POINTER(dbl), C.POINTER(dbl)]),
     "pm_graph_counts": (C.c_int, [vp, u64p, u64p]),
@@ -662,6 +663,21 @@ class PIRGraphInfo:
         _check(lib().pm_search_knn(self.h, _p(q, f32p), k, maxStep, parallel, int(benchmarking),
                                    _p(ids, i64p), _p(steps, i64p)))
         return ids, steps
+
+    def SearchKNNBatch(self, queries, k: int, maxStep: int, parallel: int, benchmarking: bool = False,
+                       return_device_queries: bool = False):
+        """GraphANNFrontend.SearchKNNBatch (graphann/search.go:236-245): SearchKNN
+        of every row of queries [nq, dim] in order (pm_search_knn_batch), on the
+        device for a non-private graph.  Returns (ids [nq, k], steps [nq, k]),
+        plus the number of queries the kernel answered if asked for."""
+        qs = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.Dim)
+        nq = qs.shape[0]
+        ids = np.zeros((nq, k), dtype=np.int64)
+        steps = np.zeros((nq, k), dtype=np.int64)
+        dq = C.c_uint64()
+        _check(lib().pm_search_knn_batch(self.h, _p(qs, f32p), nq, k, maxStep, parallel, int(benchmarking),
+                                         _p(ids, i64p), _p(steps, i64p), C.byref(dq)))
+        return (ids, steps, dq.value) if return_device_queries else (ids, steps)
 
     def SearchLoop(self, queries, k: int, step: int, parallel: int, benchmarking: bool = False):
         """private-search.go:216-240: returns (answers [q,k], online_s, maintenance_s)."""

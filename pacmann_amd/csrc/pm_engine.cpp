@@ -172,8 +172,10 @@ struct HostBuf {
 // "host_fold_*" count the maintenance fold launches by kernel (k_prep_fold_rot
 // at CS 512 / 1,024, or another form); "host_dev_steps" / "host_dev_queries"
 // the shared steps and session queries the device loop served (pm_drl.hip).
-enum HostTimer : int { HT_STEP_LAUNCH, HT_STEP_WAIT, HT_STEP_POST, HT_BATCH_QUERY, HT_GVI_PARSE, HT_SEARCH_KNN, HT_KNN_INIT, HT_KNN_BATCH, HT_KNN_UPDATE, HT_KNN_FINAL, HT_WAIT_FIRST, HT_WAIT_ALL, HT_ROWS_SEEN, HT_ROWS_TORN, HT_WAIT_DONE, HT_COMBINE, HT_COMBINE_TURN, HT_PATH_MATCH, HT_PATH_MATCH_PART, HT_PATH_MATCH_PART8, HT_PREP_SETS, HT_REC_VERIFIED, HT_REC_BAD, HT_REC_DROPPED, HT_REC_FAILED, HT_REC_PEER, HT_REC_UNEXPLAINED, HT_FOLD_ROT512, HT_FOLD_ROT1024, HT_FOLD_OTHER, HT_DEV_STEPS, HT_DEV_QUERIES, HT_COUNT };
-static const char* const kHostTimerName[HT_COUNT] = {"host_step_launch", "host_step_wait", "host_step_post", "host_batch_query", "host_gvi_parse", "host_search_knn", "host_knn_init", "host_knn_batch", "host_knn_update", "host_knn_final", "host_wait_first_token", "host_wait_all_tokens", "host_rows_seen", "host_rows_torn", "host_wait_done", "host_combine", "host_combine_turn", "host_path_match", "host_path_match_part", "host_path_match_part8", "host_prep_sets", "host_records_verified", "host_records_bad", "host_records_dropped", "host_records_failed", "host_records_peer", "host_records_unexplained", "host_fold_rot512", "host_fold_rot1024", "host_fold_other", "host_dev_steps", "host_dev_queries"};
+// "host_knn_batch_fallback": the host remainder of pm_search_knn_batch's device
+// path, one entry per call that re-ran queries whose search drew from the id stream.
+enum HostTimer : int { HT_STEP_LAUNCH, HT_STEP_WAIT, HT_STEP_POST, HT_BATCH_QUERY, HT_GVI_PARSE, HT_SEARCH_KNN, HT_KNN_INIT, HT_KNN_BATCH, HT_KNN_UPDATE, HT_KNN_FINAL, HT_WAIT_FIRST, HT_WAIT_ALL, HT_ROWS_SEEN, HT_ROWS_TORN, HT_WAIT_DONE, HT_COMBINE, HT_COMBINE_TURN, HT_PATH_MATCH, HT_PATH_MATCH_PART, HT_PATH_MATCH_PART8, HT_PREP_SETS, HT_REC_VERIFIED, HT_REC_BAD, HT_REC_DROPPED, HT_REC_FAILED, HT_REC_PEER, HT_REC_UNEXPLAINED, HT_FOLD_ROT512, HT_FOLD_ROT1024, HT_FOLD_OTHER, HT_DEV_STEPS, HT_DEV_QUERIES, HT_KNN_BATCH_FALLBACK, HT_COUNT };
+static const char* const kHostTimerName[HT_COUNT] = {"host_step_launch", "host_step_wait", "host_step_post", "host_batch_query", "host_gvi_parse", "host_search_knn", "host_knn_init", "host_knn_batch", "host_knn_update", "host_knn_final", "host_wait_first_token", "host_wait_all_tokens", "host_rows_seen", "host_rows_torn", "host_wait_done", "host_combine", "host_combine_turn", "host_path_match", "host_path_match_part", "host_path_match_part8", "host_prep_sets", "host_records_verified", "host_records_bad", "host_records_dropped", "host_records_failed", "host_records_peer", "host_records_unexplained", "host_fold_rot512", "host_fold_rot1024", "host_fold_other", "host_dev_steps", "host_dev_queries", "host_knn_batch_fallback"};
 
 struct TimedLaunch { std::string name; hipEvent_t a, b; double bytes; };
 
@@ -2000,6 +2002,10 @@ struct pm_graph {
   std::vector<VD> heap, all;
   std::vector<std::pair<VD, uint32_t>> fs;
   Clock::time_point t_init;
+  // pm_search_knn_batch's device path: a chunk's queries, answers and
+  // empty-heap flags; whether every id of the graph is < n (-1: not checked yet)
+  DevBuf kb_q, kb_ids, kb_steps, kb_flags;
+  int graph_ids_ok = -1;
   // A device-loop call that failed after queueing work (run_batched_dev) leaves
   // the session's host mirrors (FinishedBatchNum, QueriesMadeInPartition, the
   // search and dummy streams) out of step with its device state; the session
@@ -2523,6 +2529,82 @@ static int search_knn_impl(pm_graph* g, const float* query, int k, int max_step,
     knn_update(g, step);
   }
   knn_end(g, k, ids_out, steps_out);
+  return 0;
+}
+
+// GraphANNFrontend.SearchKNNBatch (graphann/search.go:236-245): SearchKNN of
+// queries[i] for i = 0 .. nq-1 in order.  Defined as that loop over
+// search_knn_impl (same ids, steps, counters and id stream afterwards); a
+// non-private in-memory graph whose shape fits k_knn_batch (pm_knnb.hip) is
+// searched on the device instead, one workgroup per query, a chunk of queries
+// per launch.  A search draws from the id stream only where a pop finds its
+// heap empty (search.go:155-159); the kernel flags such a query instead of
+// answering it, and the flagged queries are re-run here in ascending order, so
+// the stream is consumed exactly as by the loop.
+extern "C" int pm_search_knn_batch(pm_graph* g, const float* queries, uint64_t nq, int k, int max_step, int parallel,
+                                   int benchmarking, int64_t* ids, int64_t* steps, uint64_t* device_queries) {
+  if (!g) return fail(PM_EINVAL, "NULL argument");
+  CHK(check_session(g));
+  if (device_queries) *device_queries = 0;
+  if (nq && (!queries || !ids)) return fail(PM_EINVAL, "NULL argument");
+  pm_ctx* c = g->ctx;
+  const uint64_t dim = g->dim, m = g->m, ns = g->start.size(), kk = (uint64_t)std::max(k, 0);
+  auto host_query = [&](uint64_t i) {
+    return search_knn_impl(g, queries + i * dim, k, max_step, parallel, benchmarking, ids + i * kk,
+                           steps ? steps + i * kk : nullptr);
+  };
+  bool dev = nq && g->nonprivate && !g->synth && g->nshards == 1 && !benchmarking && g->dvec->p && g->graph &&
+             g->n < 0xffffffffull && k > 0 && max_step >= 0 && parallel > 0 &&
+             pmk::knn_batch_ok(dim, m, ns, (uint64_t)max_step, (uint64_t)parallel);
+  if (dev && g->graph_ids_ok < 0) {   // the kernel follows the graph's ids without a host in between
+    g->graph_ids_ok = 1;
+    for (uint64_t i = 0; i < g->n * m; ++i)
+      if (g->graph[i] >= g->n) { g->graph_ids_ok = 0; break; }
+  }
+  if (!dev || !g->graph_ids_ok) {
+    for (uint64_t i = 0; i < nq; ++i) CHK(host_query(i));
+    return 0;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  if (!g->dgraph->p) {   // the neighbour lists on the device, once per graph
+    CHK(g->dgraph->reserve(g->n * m * 4));
+    HIPCHK(hipMemcpy(g->dgraph->p, g->graph, g->n * m * 4, hipMemcpyHostToDevice));
+  }
+  const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>({nq, 1u << 15, (256ull << 20) / (kk * 16)}));
+  std::vector<uint32_t> flags(nq);
+  pmk::KnbArgs A{};
+  A.vec = g->dvec->as<float>();
+  A.graph = g->dgraph->as<uint32_t>();
+  A.start = g->dstart.as<uint32_t>();
+  A.ns = (uint32_t)ns; A.dim = (uint32_t)dim; A.m = (uint32_t)m; A.k = (uint32_t)k;
+  A.max_step = (uint32_t)max_step; A.parallel = (uint32_t)parallel;
+  A.kcap = pmk::knn_batch_kcap((uint64_t)parallel, (uint64_t)max_step, m);
+  for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const uint64_t cn = std::min(chunk, nq - q0);
+    CHK(g->kb_q.reserve(cn * dim * 4)); CHK(g->kb_ids.reserve(cn * kk * 8));
+    CHK(g->kb_steps.reserve(cn * kk * 8)); CHK(g->kb_flags.reserve(cn * 4));
+    HIPCHK(hipMemcpyAsync(g->kb_q.p, queries + q0 * dim, cn * dim * 4, hipMemcpyHostToDevice, st));
+    A.queries = g->kb_q.as<float>(); A.nq = (uint32_t)cn;
+    A.ids = g->kb_ids.as<int64_t>(); A.steps = g->kb_steps.as<int64_t>(); A.needs_host = g->kb_flags.as<uint32_t>();
+    c->timed("knn_batch", (double)cn * (double)(ns + (uint64_t)max_step * parallel * m) * (double)(dim + m) * 4.0,
+             [&] { pmk::knn_batch(st, A); });
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(ids + q0 * kk, g->kb_ids.p, cn * kk * 8, hipMemcpyDeviceToHost, st));
+    if (steps) HIPCHK(hipMemcpyAsync(steps + q0 * kk, g->kb_steps.p, cn * kk * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(flags.data() + q0, g->kb_flags.p, cn * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  uint64_t nhost = 0;
+  for (uint64_t i = 0; i < nq; ++i) nhost += flags[i] != 0;
+  g->total += (nq - nhost) * (uint64_t)max_step * (uint64_t)parallel * m;   // totalQueryNum of the device's queries
+  if (device_queries) *device_queries = nq - nhost;
+  if (nhost) {
+    auto t = Clock::now();
+    for (uint64_t i = 0; i < nq; ++i)
+      if (flags[i]) CHK(host_query(i));
+    c->host_add(HT_KNN_BATCH_FALLBACK, ms_since(t));
+  }
   return 0;
 }
 

@@ -301,6 +301,20 @@ struct DrlArgs {
   uint64_t* stamps;               // diagnostics (PM_DRL_STAMPS): [16] summed shader clocks per phase of MID rounds
 };
 
+// ---- the batched non-private search (pm_knnb.hip; pm_search_knn_batch,
+// DESIGN.md §6.5): one workgroup runs a whole SearchKNN of one query over the
+// device's vectors and graph, its state in LDS.
+struct KnbArgs {
+  const float* vec;        // [n][dim]
+  const uint32_t* graph;   // [n][m], every id < n
+  const uint32_t* start;   // [ns] the start set (GetStartVertex)
+  const float* queries;    // [nq][dim]
+  uint32_t nq, ns, dim, m, k, max_step, parallel, kcap;
+  int64_t* ids;            // [nq][k] top k by (distance, id), -1 padded
+  int64_t* steps;          // [nq][k] their reach steps
+  uint32_t* needs_host;    // [nq] 1: a pop found the heap empty (the id stream is the host's)
+};
+
 }  // namespace pm
 
 // Kernel launchers (pm_kernels.hip).  All asynchronous on `st`.
@@ -410,6 +424,15 @@ void prf_batch(hipStream_t st, const uint32_t* rk, const uint64_t* tags, const u
 void team_round(hipStream_t st, const DrlArgs& A, PmEvents ev = {});
 uint32_t team_round_lds(uint32_t kcap, uint32_t n, uint32_t m);   // bytes of dynamic LDS
 constexpr uint32_t kDrlMaxKcap = 4096, kDrlMaxN = 256, kDrlMaxNM = 8192, kDrlMaxParallel = 8;
+// the batched non-private search (pm_knnb.hip): one 256-thread workgroup per
+// query.  knn_batch_kcap: known-set capacity, the next power of two >=
+// parallel (1 + max_step m) (0: beyond any LDS); knn_batch_lds: bytes of
+// dynamic LDS; knn_batch_ok: whether the shape runs on the device.
+constexpr uint32_t kKnbMaxBatch = 256, kKnbMaxM = 64, kKnbMaxLds = 160 * 1024 - 512;
+uint32_t knn_batch_kcap(uint64_t parallel, uint64_t max_step, uint64_t m);
+uint64_t knn_batch_lds(uint32_t kcap, uint32_t dim, uint32_t nb, uint32_t ns);
+bool knn_batch_ok(uint64_t dim, uint64_t m, uint64_t ns, uint64_t max_step, uint64_t parallel);
+void knn_batch(hipStream_t st, const KnbArgs& A);
 // graph construction and ground truth (pm_graph.hip)
 uint32_t knn_pad_dim(uint32_t dim);   // bf16 row width for the prefilter (0: unsupported)
 uint32_t knn_top();                   // prefilter candidates per query row
