@@ -2,31 +2,7 @@
 // engine (device-resident DB, hints and client state; batched steps), the
 // graphann beam search over PIRGraphInfo, and the extern "C" boundary of
 // include/pacmann.h.
-#include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>   // types only: the functions are resolved at run time (rccl_api)
-
-#include <algorithm>
-#include <atomic>
-#include <cstdio>
-#include <cstdlib>
-#include <chrono>
-#include <condition_variable>
-#include <cmath>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <mutex>
-#include <thread>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/pacmann.h"
-#include "pm_aes.h"
-#define PM_HOST_TU 1
-#include "pm_internal.h"
-
-using namespace pm;
+#include "pm_host.h"
 
 // Open-addressing uint64 -> uint32 map with O(1) clear (generation stamps).
 // Replaces node-allocating std::unordered_map on the per-round host path
@@ -76,358 +52,10 @@ struct FlatMap {
   }
 };
 
-// ---------------------------------------------------------------------------
-// errors
-// ---------------------------------------------------------------------------
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess)                                                                 \
-      return fail(PM_EHIP, std::string(#x) + ": " + hipGetErrorString(e_));               \
-  } while (0)
-#define CHK(x)            \
-  do {                    \
-    int r_ = (x);         \
-    if (r_ != 0) return r_; \
-  } while (0)
-
-extern "C" const char* pm_last_error(void) { return g_err.c_str(); }
-
-// ---------------------------------------------------------------------------
-// host AES-128 key schedule (FIPS-197 §5.2; expandKeyAsm, aes_amd64.s:87-126)
-// ---------------------------------------------------------------------------
-static constexpr AesTables kAes{};
-extern "C" int pm_expand_key(const uint8_t key[16], uint32_t rk[44]) {
-  uint8_t w[176];
-  memcpy(w, key, 16);
-  uint8_t rcon = 1;
-  for (int i = 16; i < 176; i += 4) {
-    uint8_t t[4] = {w[i - 4], w[i - 3], w[i - 2], w[i - 1]};
-    if (i % 16 == 0) {
-      uint8_t u = t[0];
-      t[0] = kAes.sbox[t[1]] ^ rcon; t[1] = kAes.sbox[t[2]]; t[2] = kAes.sbox[t[3]]; t[3] = kAes.sbox[u];
-      rcon = AesTables::gmul(rcon, 2);
-    }
-    for (int k = 0; k < 4; ++k) w[i + k] = w[i - 16 + k] ^ t[k];
-  }
-  memcpy(rk, w, 176);   // little-endian word view, as the GPU and AESENC read it
-  return 0;
-}
 static void derive_key(uint64_t seed, uint64_t part, uint64_t epoch, uint8_t key[16]) {
   uint64_t r1 = hash4(seed, DOM_KEY, part, epoch, 0), r2 = hash4(seed, DOM_KEY, part, epoch, 1);
   memcpy(key, &r1, 8);
   memcpy(key + 8, &r2, 8);
-}
-
-// ---------------------------------------------------------------------------
-// context, device buffers, timing
-// ---------------------------------------------------------------------------
-struct DevBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int reserve(size_t bytes) {
-    if (bytes <= n) return 0;
-    if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-    if (bytes == 0) return 0;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) return fail(PM_ENOMEM, "hipMalloc(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
-    n = bytes;
-    return 0;
-  }
-  template <class T> T* as() const { return (T*)p; }
-};
-// Pinned host memory the GPU reads (step descriptor) and writes (results)
-// zero-copy.  It must be fine-grained (coherent): with the default
-// coarse-grained allocation the GPU may serve the descriptor from a stale L2
-// line and the host may read result rows before the device writes land.
-struct HostBuf {
-  void* p = nullptr;
-  size_t n = 0;
-  ~HostBuf() { if (p) (void)hipHostFree(p); }
-  int reserve(size_t bytes) {
-    if (bytes <= n) return 0;
-    if (p) { (void)hipHostFree(p); p = nullptr; n = 0; }
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocCoherent | hipHostMallocMapped);
-    if (e != hipSuccess) return fail(PM_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-    memset(p, 0, bytes);   // no stale step token (PmOutHdr::token is never 0)
-    n = bytes;
-    return 0;
-  }
-  template <class T> T* as() const { return (T*)p; }
-};
-
-// Host wall-clock accumulators, read back as "host_*" through pm_timing_get.
-// The "host_path_*" entries count the hint-search kernel each step launched
-// (k_match / k_match_part / k_match_part8; total_ms 0), "host_prep_sets" the
-// re-preprocessing launch sets of the serving loops, with total_ms = the number
-// of clients they folded (a count, not a time).
-// The "host_records_*" entries count the sharded loop's record checks
-// (pm_set_option "verify_records"): answered records equal to the graph's row
-// and the reference-order L2 (verified) or not (bad); unanswered ids explained
-// by the batch layer's overflow drop (dropped), by a failed sub-query of this
-// rank (failed), by another rank's sub-query (peer), or not at all (unexplained).
-// "host_fold_*" count the maintenance fold launches by kernel (k_prep_fold_rot
-// at CS 512 / 1,024, or another form); "host_dev_steps" / "host_dev_queries"
-// the shared steps and session queries the device loop served (pm_drl.hip).
-// "host_knn_batch_fallback": the host remainder of pm_search_knn_batch's device
-// path, one entry per call that re-ran queries whose search drew from the id stream.
-enum HostTimer : int { HT_STEP_LAUNCH, HT_STEP_WAIT, HT_STEP_POST, HT_BATCH_QUERY, HT_GVI_PARSE, HT_SEARCH_KNN, HT_KNN_INIT, HT_KNN_BATCH, HT_KNN_UPDATE, HT_KNN_FINAL, HT_WAIT_FIRST, HT_WAIT_ALL, HT_ROWS_SEEN, HT_ROWS_TORN, HT_WAIT_DONE, HT_COMBINE, HT_COMBINE_TURN, HT_PATH_MATCH, HT_PATH_MATCH_PART, HT_PATH_MATCH_PART8, HT_PREP_SETS, HT_REC_VERIFIED, HT_REC_BAD, HT_REC_DROPPED, HT_REC_FAILED, HT_REC_PEER, HT_REC_UNEXPLAINED, HT_FOLD_ROT512, HT_FOLD_ROT1024, HT_FOLD_OTHER, HT_DEV_STEPS, HT_DEV_QUERIES, HT_KNN_BATCH_FALLBACK, HT_COUNT };
-static const char* const kHostTimerName[HT_COUNT] = {"host_step_launch", "host_step_wait", "host_step_post", "host_batch_query", "host_gvi_parse", "host_search_knn", "host_knn_init", "host_knn_batch", "host_knn_update", "host_knn_final", "host_wait_first_token", "host_wait_all_tokens", "host_rows_seen", "host_rows_torn", "host_wait_done", "host_combine", "host_combine_turn", "host_path_match", "host_path_match_part", "host_path_match_part8", "host_prep_sets", "host_records_verified", "host_records_bad", "host_records_dropped", "host_records_failed", "host_records_peer", "host_records_unexplained", "host_fold_rot512", "host_fold_rot1024", "host_fold_other", "host_dev_steps", "host_dev_queries", "host_knn_batch_fallback"};
-
-struct TimedLaunch { std::string name; hipEvent_t a, b; double bytes; };
-
-struct pm_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int timing = 0;   // 0 off, 1 preprocessing / leaf kernels, 2 also the per-step kernels,
-                    // 3 as 2 with the shared steps' kernels timed on every kSampleSteps-th step
-  // timing 3: whether the current shared step's kernels carry events (group_step)
-  bool sample_now = true;
-  uint64_t sample_ctr = 0;
-  bool no_fuse = false;      // PM_NO_FUSE=1: the three step kernels even when k_step fits
-  bool no_split = false;     // PM_NO_SPLIT=1: k_answer gathers wide sets itself (no k_gather)
-  bool no_guess = false;     // PM_NO_GUESS=1: k_step answers do not start before their resolution
-  bool verify_rows = false;  // PM_VERIFY_ROWS=1: re-read each step's results after the stream drains
-  bool debug_cache = false;  // PM_DEBUG_CACHE=1: check cached answers against the slot's first answer
-  bool log_steps = false;    // PM_LOG_STEPS=1: one stderr line per sub-query per step
-  bool debug_sync = false;   // PM_DEBUG_SYNC=1: synchronise after every launch (fault triage)
-  // Maintenance: the replacement rows (HBM copies, independent of the PRF
-  // tables and the fold) run on a side stream beside k_prep_offsets
-  // (PM_REPL_SIDE=0: after the fold on the one stream; timed runs keep that
-  // order so every launch carries its own events)
-  bool repl_side = true;
-  hipStream_t side = nullptr;
-  hipEvent_t side_ev[2] = {};
-  std::mutex side_mu;
-  // Result rows vs their header checksum when the token is first seen
-  // (PmOutHdr::csum): 0 = no check, 1 = count a mismatch ("host_rows_torn")
-  // and fail the step, 2 = count it and wait for the row to match (PM_ROWS_CHECK)
-  int rows_check = 2;
-  std::vector<uint64_t> hash_mult;   // row_hash_mult(w) for every word a row can have
-  // Step completion (result publication): an event recorded
-  // after the step's last kernel, with a system-scope release, so that once
-  // hipEventQuery reports it, every result byte the step wrote into pinned
-  // memory is visible to the host (HIP event semantics; the header tokens
-  // alone give no such order).  One worker queries the runtime, the others read
-  // an atomic.
-  // Steps of several engines (or a session's own steps beside its group's)
-  // can share one context, so completions are counted per context: record_done
-  // returns the step's sequence number (counted after the record), done_seen
-  // is the highest one known complete.  A later record of the event covers
-  // the earlier steps of the stream.
-  // PM_PUBLISH_WAIT=0: the token + row-hash acceptance alone (diagnostics).
-  // Each step's completion has an event of its own in a ring (step seq uses
-  // done_ring[seq % kDoneRing]): a waiter for step seq queries that step's
-  // event, not the newest one, so it never waits for steps recorded after its
-  // own (a slot re-recorded 64 steps later still completes after it: one stream).
-  bool publish_wait = true;
-  static constexpr uint32_t kDoneRing = 64;
-  hipEvent_t done_ev = nullptr;   // done_ring[0] (creation check)
-  hipEvent_t done_ring[kDoneRing] = {};
-  std::atomic<uint64_t> done_rec{0}, done_seen{0};
-  std::mutex done_mu, rec_mu;
-  uint64_t record_done(hipStream_t st) {
-    if (!publish_wait) return 0;
-    std::lock_guard<std::mutex> lk(rec_mu);
-    const uint64_t seq = done_rec.load(std::memory_order_relaxed) + 1;
-    (void)hipEventRecord(done_ring[seq % kDoneRing], st);
-    done_rec.store(seq, std::memory_order_release);
-    return seq;
-  }
-  std::string last_kernel;
-  // host-side wall-clock accumulators ("host_*" names in pm_timing_get)
-  uint64_t host_n[HT_COUNT] = {};
-  double host_ms[HT_COUNT] = {};
-  void host_add(HostTimer t, double ms) { host_n[t]++; host_ms[t] += ms; }
-  void count_match_path(int path) {
-    host_add(path == pmk::MATCH_PART8 ? HT_PATH_MATCH_PART8 : path == pmk::MATCH_PART ? HT_PATH_MATCH_PART : HT_PATH_MATCH, 0.0);
-  }
-  std::vector<TimedLaunch> launches;
-  std::vector<hipEvent_t> pool;
-  hipEvent_t ev() {
-    if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
-    hipEvent_t e; (void)hipEventCreate(&e); return e;
-  }
-  // Bracket a launch with events on the stream it runs on (when enabled).
-  template <class F> void timed(const char* name, double bytes, F&& f, int level = 1) {
-    last_kernel = name;
-    if (debug_sync) {
-      f();
-      hipError_t e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) fprintf(stderr, "[pm] kernel %s failed: %s\n", name, hipGetErrorString(e));
-      return;
-    }
-    if (timing < level) { f(); return; }
-    TimedLaunch t{name, ev(), ev(), bytes};
-    (void)hipEventRecord(t.a, stream);
-    f();
-    (void)hipEventRecord(t.b, stream);
-    launches.push_back(t);
-  }
-  // The same for launchers that attach the events to the kernel's own dispatch
-  // packet (hipExtLaunchKernelGGL): no marker latency around short kernels.
-  template <class F> void timed_ext(const char* name, double bytes, F&& f, int level) {
-    last_kernel = name;
-    if (debug_sync) { timed(name, bytes, [&] { f(pmk::PmEvents{}); }, level); return; }
-    if (timing < level || (timing == 3 && level == 2 && !sample_now)) { f(pmk::PmEvents{}); return; }
-    TimedLaunch t{name, ev(), ev(), bytes};
-    f(pmk::PmEvents{t.a, t.b});
-    launches.push_back(t);
-  }
-  ~pm_ctx() {
-    for (auto& t : launches) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-    for (auto e : pool) (void)hipEventDestroy(e);
-    for (auto e : done_ring) if (e) (void)hipEventDestroy(e);
-    for (auto e : side_ev) if (e) (void)hipEventDestroy(e);
-    if (side) (void)hipStreamDestroy(side);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-extern "C" int pm_ctx_create(int device, pm_ctx** out) {
-  if (!out) return fail(PM_EINVAL, "out is NULL");
-  int n = 0;
-  HIPCHK(hipGetDeviceCount(&n));
-  if (device < 0 || device >= n) return fail(PM_EINVAL, "no such HIP device " + std::to_string(device));
-  HIPCHK(hipSetDevice(device));
-  // Each online step ends in one host wait; spin instead of yielding so the
-  // host resumes the beam search as soon as the GPU finishes.  Ignored if the
-  // device is already initialised with other flags.
-  (void)hipSetDeviceFlags(hipDeviceScheduleSpin);
-  (void)hipGetLastError();
-  pm_ctx* c = new pm_ctx();
-  c->device = device;
-  const char* dbg = getenv("PM_DEBUG_SYNC");
-  c->debug_sync = dbg && dbg[0] == '1';
-  const char* nf = getenv("PM_NO_FUSE");
-  c->no_fuse = nf && nf[0] == '1';
-  const char* ns = getenv("PM_NO_SPLIT");
-  c->no_split = ns && ns[0] == '1';
-  const char* ls = getenv("PM_LOG_STEPS");
-  c->log_steps = ls && ls[0] == '1';
-  const char* dc = getenv("PM_DEBUG_CACHE");
-  c->debug_cache = dc && dc[0] == '1';
-  const char* vr = getenv("PM_VERIFY_ROWS");
-  c->verify_rows = vr && vr[0] == '1';
-  if (const char* rc = getenv("PM_ROWS_CHECK")) c->rows_check = atoi(rc);
-  c->hash_mult.resize(pmk::step_max_e());
-  for (size_t w = 0; w < c->hash_mult.size(); ++w) c->hash_mult[w] = row_hash_mult(w);
-  if (const char* pw = getenv("PM_PUBLISH_WAIT")) c->publish_wait = pw[0] != '0';
-  if (c->publish_wait) {
-    for (auto& e : c->done_ring)
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventReleaseToSystem) != hipSuccess) {
-        delete c;
-        return fail(PM_EHIP, "hipEventCreateWithFlags(step completion) failed");
-      }
-    c->done_ev = c->done_ring[0];
-  }
-  if (const char* rs = getenv("PM_REPL_SIDE")) c->repl_side = rs[0] != '0';
-  const char* ng = getenv("PM_NO_GUESS");
-  c->no_guess = ng && ng[0] == '1';
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) { delete c; return fail(PM_EHIP, hipGetErrorString(e)); }
-  *out = c;
-  return 0;
-}
-extern "C" void pm_ctx_destroy(pm_ctx* c) { if (c) { (void)hipSetDevice(c->device); delete c; } }
-extern "C" int pm_ctx_sync(pm_ctx* c) { HIPCHK(hipStreamSynchronize(c->stream)); HIPCHK(hipGetLastError()); return 0; }
-extern "C" int pm_ctx_mem_info(pm_ctx* c, uint64_t* free_b, uint64_t* total_b) {
-  if (!c) return fail(PM_EINVAL, "ctx is NULL");
-  HIPCHK(hipSetDevice(c->device));
-  size_t f = 0, t = 0;
-  HIPCHK(hipMemGetInfo(&f, &t));
-  if (free_b) *free_b = f;
-  if (total_b) *total_b = t;
-  return 0;
-}
-// Timeline base: one event recorded when kernel timing is first enabled in the
-// process; every timed launch's start / end can then be placed on one time axis
-// (hipEventElapsedTime between events of one device, any streams).
-static std::mutex g_tl_mu;
-static hipEvent_t g_tl_base = nullptr;
-extern "C" int pm_timing_enable(pm_ctx* c, int on) {
-  c->timing = on;
-  if (on >= 2) {
-    std::lock_guard<std::mutex> lk(g_tl_mu);
-    if (!g_tl_base) {
-      HIPCHK(hipEventCreate(&g_tl_base));
-      HIPCHK(hipEventRecord(g_tl_base, c->stream));
-    }
-  }
-  return 0;
-}
-// Diagnostics: append "name,start_us,end_us,ctx" for every timed launch of c
-// (relative to the process's timeline base) to `path`.
-extern "C" int pm_timing_timeline(pm_ctx* c, const char* path) {
-  if (!c || !path) return fail(PM_EINVAL, "NULL argument");
-  HIPCHK(hipStreamSynchronize(c->stream));
-  std::lock_guard<std::mutex> lk(g_tl_mu);
-  if (!g_tl_base) return fail(PM_EINVAL, "no timeline (kernel timing level 2 never enabled)");
-  FILE* f = fopen(path, "a");
-  if (!f) return fail(PM_EINVAL, std::string("cannot open ") + path);
-  for (auto& t : c->launches) {
-    float a = 0, b = 0;
-    if (hipEventElapsedTime(&a, g_tl_base, t.a) != hipSuccess || hipEventElapsedTime(&b, g_tl_base, t.b) != hipSuccess)
-      continue;
-    fprintf(f, "%s,%.3f,%.3f,%p\n", t.name.c_str(), a * 1e3, b * 1e3, (void*)c);
-  }
-  fclose(f);
-  return 0;
-}
-// "verify_records" (sharded loop): check the records of every value-th shared
-// step of each team on the host (0: off); read when a loop starts
-static std::atomic<int> g_verify_records{0};
-// "device_loop": pm_search_loop_batched's device loop (run_batched_dev) 1 / 0;
-// -1: the environment's choice (PM_DEVICE_LOOP, default 1)
-static std::atomic<int> g_device_loop{-1};
-// Bound on the communicators' creation and on the probe (pm_set_option
-// "rccl_timeout_s", else PM_RCCL_TIMEOUT_S, default 120 s): a rank whose peer
-// never joins returns PM_ETIMEDOUT instead of blocking inside RCCL.
-static std::atomic<int> g_rccl_timeout_s{-1};
-// fault seam (tests): run_batched_dev fails before queueing query n (-1: off)
-static std::atomic<int> g_fault_drl_query{-1};
-extern "C" int pm_set_option(const char* name, int value) {
-  if (!name) return fail(PM_EINVAL, "NULL argument");
-  if (!strcmp(name, "verify_records")) { g_verify_records.store(value < 0 ? 0 : value); return 0; }
-  if (!strcmp(name, "rccl_timeout_s")) { g_rccl_timeout_s.store(value); return 0; }
-  if (!strcmp(name, "device_loop")) { g_device_loop.store(value < 0 ? -1 : value); return 0; }
-  if (!strcmp(name, "fault_drl_query")) { g_fault_drl_query.store(value); return 0; }
-  if (!strcmp(name, "aes_bs")) { pmk::set_aes_bs(value); return 0; }
-  if (pmk::set_option(name, value)) return fail(PM_EINVAL, std::string("unknown option ") + name);
-  return 0;
-}
-extern "C" int pm_timing_reset(pm_ctx* c) {
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (auto& t : c->launches) { c->pool.push_back(t.a); c->pool.push_back(t.b); }
-  c->launches.clear();
-  for (int i = 0; i < HT_COUNT; ++i) { c->host_n[i] = 0; c->host_ms[i] = 0; }
-  return 0;
-}
-extern "C" int pm_timing_get(pm_ctx* c, const char* name, uint64_t* launches, double* total_ms,
-                             double* bytes) {
-  HIPCHK(hipStreamSynchronize(c->stream));
-  uint64_t n = 0; double ms = 0, by = 0;
-  if (strncmp(name, "host_", 5) == 0) {
-    for (int i = 0; i < HT_COUNT; ++i)
-      if (strcmp(name, kHostTimerName[i]) == 0) { n = c->host_n[i]; ms = c->host_ms[i]; }
-    if (launches) *launches = n;
-    if (total_ms) *total_ms = ms;
-    if (bytes) *bytes = 0;
-    return 0;
-  }
-  for (auto& t : c->launches) {
-    if (t.name != name) continue;
-    float x = 0;
-    HIPCHK(hipEventElapsedTime(&x, t.a, t.b));
-    ++n; ms += x; by += t.bytes;
-  }
-  if (launches) *launches = n;
-  if (total_ms) *total_ms = ms;
-  if (bytes) *bytes = by;
-  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -489,24 +117,6 @@ static inline void step_read_window(PmStep& S, size_t pf_off, size_t pf_len, uin
 static inline uint32_t host_rows_partial(const pm_ctx* c, bool partial) {
   return partial && !c->verify_rows && !c->debug_cache ? 1u : 0u;
 }
-#if defined(PM_STEP_STAMPS) || defined(PM_MR_STAMPS) || defined(PM_ANSWER_STAMPS)
-// Stamp builds: drain st, then append `hdr` and the first `count` words of
-// `buf` to the file at `path`.
-static int dump_stamps(hipStream_t st, const char* path, const void* hdr, size_t hdr_bytes, const DevBuf& buf, uint64_t count) {
-  HIPCHK(hipStreamSynchronize(st));
-  std::vector<uint64_t> t(count);
-  HIPCHK(hipMemcpy(t.data(), buf.p, count * 8, hipMemcpyDeviceToHost));
-  static std::mutex mu;   // the teams' launching workers share the file
-  std::lock_guard<std::mutex> lk(mu);
-  if (FILE* f = fopen(path, "ab")) {
-    fwrite(hdr, 1, hdr_bytes, f);
-    fwrite(t.data(), 8, count, f);
-    fclose(f);
-  }
-  return 0;
-}
-#endif
-
 // ---------------------------------------------------------------------------
 // PianoPIR engine: P partitions (P = 1 for PianoPIR, BatchSize/2 for the batch)
 // ---------------------------------------------------------------------------
@@ -973,10 +583,6 @@ static int engine_prep(Engine* g, uint64_t p0, uint64_t p1) {
 // read zero-copy from pinned host memory and the results (status header +
 // entry + L2 distance to q) are written by the GPU straight into pinned host
 // memory, so a step costs three launches and one stream synchronisation.
-using Clock = std::chrono::steady_clock;
-static inline double ms_since(Clock::time_point t) {
-  return std::chrono::duration<double, std::milli>(Clock::now() - t).count();
-}
 
 // Completion of a step.  Every result header in pinned memory carries this
 // step's token; the host polls the tokens (and prefetches the bytes [pf_off,
@@ -1840,101 +1446,6 @@ extern "C" int pm_batchpir_export(pm_batchpir* h, uint64_t p, uint32_t* rk, uint
                                   uint64_t* hist) {
   if (p >= h->e.P || !h->e.parts[p].owned) return fail(PM_EINVAL, "partition not held by this shard");
   return engine_export(&h->e, p, rk, pt, par, pp, bt, bpar, ri, rv, hist);
-}
-
-// ---------------------------------------------------------------------------
-// leaf batches
-// ---------------------------------------------------------------------------
-extern "C" int pm_prf_batch(pm_ctx* c, const uint32_t rk[44], const uint64_t* tags, const uint64_t* xs,
-                            uint64_t n, uint64_t* out) {
-  if (n == 0) return 0;
-  DevBuf drk, dt, dx, dout;
-  CHK(drk.reserve(176)); CHK(dt.reserve(n * 8)); CHK(dx.reserve(n * 8)); CHK(dout.reserve(n * 8));
-  hipStream_t st = c->stream;
-  HIPCHK(hipMemcpyAsync(drk.p, rk, 176, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dt.p, tags, n * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dx.p, xs, n * 8, hipMemcpyHostToDevice, st));
-  c->timed("prf", (double)n, [&] { pmk::prf_batch(st, drk.as<uint32_t>(), dt.as<uint64_t>(), dx.as<uint64_t>(), n, dout.as<uint64_t>()); });
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, dout.p, n * 8, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
-}
-extern "C" int pm_l2_batch(pm_ctx* c, const float* q, const float* rows, uint64_t nrows, uint64_t dim,
-                           float* out) {
-  if (nrows == 0) return 0;
-  if (dim == 0) return fail(PM_EINVAL, "dim must be > 0");
-  DevBuf dq, dr, dout;
-  CHK(dq.reserve(dim * 4)); CHK(dr.reserve(nrows * dim * 4)); CHK(dout.reserve(nrows * 4));
-  hipStream_t st = c->stream;
-  HIPCHK(hipMemcpyAsync(dq.p, q, dim * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(dr.p, rows, nrows * dim * 4, hipMemcpyHostToDevice, st));
-  c->timed("l2_rows", (double)nrows * dim * 4, [&] {
-    pmk::l2_rows(st, dr.as<float>(), dim, nrows, nullptr, dq.as<float>(), (uint32_t)dim, dout.as<float>());
-  });
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out, dout.p, nrows * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
-}
-extern "C" int pm_ip_batch(pm_ctx* c, const uint32_t* q, const uint32_t* rows, uint64_t nrows, uint64_t dim,
-                           uint32_t* per_row, uint32_t* sum) {
-  if (dim == 0) return fail(PM_EINVAL, "dim must be > 0");
-  DevBuf dq, dr, dpr, ds;
-  CHK(dq.reserve(dim * 4)); CHK(dr.reserve(std::max<uint64_t>(1, nrows * dim * 4)));
-  CHK(dpr.reserve(std::max<uint64_t>(4, nrows * 4))); CHK(ds.reserve(4));
-  hipStream_t st = c->stream;
-  HIPCHK(hipMemcpyAsync(dq.p, q, dim * 4, hipMemcpyHostToDevice, st));
-  if (nrows) HIPCHK(hipMemcpyAsync(dr.p, rows, nrows * dim * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(ds.p, 0, 4, st));
-  c->timed("ip_scan", (double)nrows * dim * 4, [&] {
-    pmk::ip_rows(st, dr.as<uint32_t>(), nrows, dq.as<uint32_t>(), (uint32_t)dim, per_row ? dpr.as<uint32_t>() : nullptr,
-                 ds.as<uint32_t>());
-  });
-  HIPCHK(hipGetLastError());
-  if (per_row && nrows) HIPCHK(hipMemcpyAsync(per_row, dpr.p, nrows * 4, hipMemcpyDeviceToHost, st));
-  uint32_t s = 0;
-  HIPCHK(hipMemcpyAsync(&s, ds.p, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (sum) *sum = s;
-  return 0;
-}
-extern "C" int pm_ip_bench(pm_ctx* c, uint64_t N, uint64_t D, uint32_t* sum, double* scan_ms) {
-  return pm_ip_bench_shard(c, N, D, 0, N, sum, scan_ms);
-}
-extern "C" int pm_ip_bench_shard(pm_ctx* c, uint64_t Ntot, uint64_t D, uint64_t r0, uint64_t N, uint32_t* sum,
-                                 double* scan_ms) {
-  if (!c) return fail(PM_EINVAL, "NULL context");
-  if (D == 0 || D % 4 || D > 4096) return fail(PM_EINVAL, "D must be a multiple of 4 and <= 4096");
-  if (r0 > Ntot || N > Ntot - r0) return fail(PM_EINVAL, "shard rows past the fill's N");
-  if (N == 0) {   // an empty shard adds nothing
-    if (sum) *sum = 0;
-    if (scan_ms) *scan_ms = 0.0;
-    return 0;
-  }
-  DevBuf dv, dq, ds;
-  CHK(dv.reserve(N * D * 4)); CHK(dq.reserve(D * 4)); CHK(ds.reserve(4));
-  std::vector<uint32_t> q(D);
-  for (uint64_t j = 0; j < D; ++j) q[j] = (uint32_t)j;
-  hipStream_t st = c->stream;
-  HIPCHK(hipMemcpyAsync(dq.p, q.data(), D * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(ds.p, 0, 4, st));
-  pmk::ip_fill(st, dv.as<uint32_t>(), N, (uint32_t)D, r0);
-  hipEvent_t a, b;
-  HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-  HIPCHK(hipEventRecord(a, st));
-  c->timed("ip_scan", (double)N * D * 4, [&] { pmk::ip_rows(st, dv.as<uint32_t>(), N, dq.as<uint32_t>(), (uint32_t)D, nullptr, ds.as<uint32_t>()); });
-  HIPCHK(hipEventRecord(b, st));
-  HIPCHK(hipGetLastError());
-  uint32_t s = 0;
-  HIPCHK(hipMemcpyAsync(&s, ds.p, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, a, b));
-  (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-  if (sum) *sum = s;
-  if (scan_ms) *scan_ms = ms;
-  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -4605,245 +4116,6 @@ extern "C" int pm_search_loop_batched(pm_graph** gs, uint32_t S, const float* qu
   return 0;
 }
 
-// ---- the library-native combine: RCCL over xGMI (no Python on the step path) ----
-// RCCL is resolved with dlopen on first use, not linked: the library loads on
-// CPU-only machines, and a process that already mapped RCCL (torch's ROCm
-// wheel ships librccl.so.1 too) shares that one copy (RTLD_NOLOAD by SONAME).
-struct RcclApi {
-  void* h = nullptr;
-  std::string err;
-  decltype(&ncclGetUniqueId) get_unique_id = nullptr;
-  decltype(&ncclCommInitRank) comm_init_rank = nullptr;
-  decltype(&ncclAllReduce) all_reduce = nullptr;
-  decltype(&ncclCommDestroy) comm_destroy = nullptr;
-  decltype(&ncclGetErrorString) error_string = nullptr;
-  // the nonblocking forms (optional: an RCCL without them gets a watched blocking init)
-  decltype(&ncclCommInitRankConfig) comm_init_rank_config = nullptr;
-  decltype(&ncclCommGetAsyncError) get_async_error = nullptr;
-  decltype(&ncclCommAbort) comm_abort = nullptr;
-  decltype(&ncclGroupStart) group_start = nullptr;
-  decltype(&ncclGroupEnd) group_end = nullptr;
-  bool nonblocking() const { return comm_init_rank_config && get_async_error && comm_abort && group_start && group_end; }
-};
-static const RcclApi& rccl_api() {
-  static const RcclApi api = [] {
-    RcclApi a;
-    a.h = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
-    if (!a.h) a.h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!a.h) a.h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!a.h) { const char* e = dlerror(); a.err = e ? e : "dlopen(librccl.so.1) failed"; return a; }
-    a.get_unique_id = (decltype(a.get_unique_id))dlsym(a.h, "ncclGetUniqueId");
-    a.comm_init_rank = (decltype(a.comm_init_rank))dlsym(a.h, "ncclCommInitRank");
-    a.all_reduce = (decltype(a.all_reduce))dlsym(a.h, "ncclAllReduce");
-    a.comm_destroy = (decltype(a.comm_destroy))dlsym(a.h, "ncclCommDestroy");
-    a.error_string = (decltype(a.error_string))dlsym(a.h, "ncclGetErrorString");
-    a.comm_init_rank_config = (decltype(a.comm_init_rank_config))dlsym(a.h, "ncclCommInitRankConfig");
-    a.get_async_error = (decltype(a.get_async_error))dlsym(a.h, "ncclCommGetAsyncError");
-    a.comm_abort = (decltype(a.comm_abort))dlsym(a.h, "ncclCommAbort");
-    a.group_start = (decltype(a.group_start))dlsym(a.h, "ncclGroupStart");
-    a.group_end = (decltype(a.group_end))dlsym(a.h, "ncclGroupEnd");
-    if (!a.get_unique_id || !a.comm_init_rank || !a.all_reduce || !a.comm_destroy || !a.error_string)
-      a.err = "librccl.so.1 lacks an NCCL entry point";
-    return a;
-  }();
-  return api;
-}
-#define RCCLCHK(call)                                                                              \
-  do {                                                                                             \
-    const ncclResult_t r_ = (call);                                                                \
-    if (r_ != ncclSuccess) return fail(PM_EHIP, std::string(#call ": ") + rccl_api().error_string(r_)); \
-  } while (0)
-
-// (rccl_timeout_s: g_rccl_timeout_s, with pm_set_option)
-static double rccl_timeout_s() {
-  const int o = g_rccl_timeout_s.load();
-  if (o > 0) return o;
-  const char* e = getenv("PM_RCCL_TIMEOUT_S");
-  return e && atof(e) > 0 ? atof(e) : 120.0;
-}
-
-struct pm_rccl {
-  int device = 0, nranks = 1, rank = 0;
-  bool nonblocking = false;        // communicators made with config.blocking = 0: calls may return ncclInProgress
-  std::vector<ncclComm_t> comms;   // one per lock-step team: a team's collectives never wait for another's
-  bool aborted = false;
-  void abort_all() {
-    for (ncclComm_t& c : comms)
-      if (c) { (void)(rccl_api().comm_abort ? rccl_api().comm_abort(c) : rccl_api().comm_destroy(c)); c = nullptr; }
-    aborted = true;
-  }
-  ~pm_rccl() {
-    for (ncclComm_t c : comms)
-      if (c) (void)rccl_api().comm_destroy(c);
-  }
-};
-// A call on a nonblocking communicator: ncclInProgress means "issued, not yet
-// complete" -- poll the communicator's state until it settles (or the bound).
-static ncclResult_t rccl_settle(const pm_rccl* r, ncclComm_t c, ncclResult_t res, double limit_s) {
-  if (res != ncclInProgress || !r->nonblocking) return res;
-  const auto t0 = Clock::now();
-  ncclResult_t st = ncclInProgress;
-  for (uint64_t polls = 0;; ++polls) {
-    if (rccl_api().get_async_error(c, &st) != ncclSuccess) return ncclInternalError;
-    if (st != ncclInProgress) return st;
-    if (std::chrono::duration<double>(Clock::now() - t0).count() > limit_s) return ncclInProgress;
-    // yield: RCCL's own proxy / init threads share the host cores with this poll
-    std::this_thread::sleep_for(std::chrono::microseconds(polls < 100 ? 10 : 200));
-  }
-}
-
-extern "C" int pm_rccl_unique_id(uint8_t id[PM_RCCL_ID_BYTES]) {
-  if (!id) return fail(PM_EINVAL, "NULL argument");
-  const RcclApi& a = rccl_api();
-  if (!a.err.empty()) return fail(PM_EHIP, "RCCL unavailable: " + a.err);
-  static_assert(sizeof(ncclUniqueId) == PM_RCCL_ID_BYTES, "ncclUniqueId size");
-  ncclUniqueId u;
-  RCCLCHK(a.get_unique_id(&u));
-  memcpy(id, &u, sizeof u);
-  return 0;
-}
-
-// The teams' communicators, created within rccl_timeout_s() by ONE path (round
-// 6): nonblocking inits (ncclCommInitRankConfig, config.blocking = 0) issued
-// as one ncclGroupStart / ncclGroupEnd group -- NCCL's rule for several
-// communicators created by one thread; round 5's ungrouped nonblocking inits
-// never settled on the GPU box -- then each communicator's state polled with a
-// yield (ncclCommGetAsyncError, 10-200 us sleeps) until it settles or the bound
-// expires.  On an error or the bound every communicator is aborted
-// (ncclCommAbort: RCCL's own init work ends), so no thread of this library is
-// ever left inside RCCL; a rank whose peer never joined gets PM_ETIMEDOUT.
-// An RCCL without the nonblocking API is refused (PM_EHIP): callers fall back.
-static bool rccl_debug() {
-  static const bool on = [] { const char* e = getenv("PM_RCCL_DEBUG"); return e && e[0] == '1'; }();
-  return on;
-}
-extern "C" int pm_rccl_create(int device, int nranks, int rank, const uint8_t* ids, uint32_t nteams, pm_rccl** out) {
-  if (!ids || !out || nteams == 0 || nranks < 1 || rank < 0 || rank >= nranks) return fail(PM_EINVAL, "bad argument");
-  *out = nullptr;
-  const double limit = rccl_timeout_s();
-  // fault seams (tests): this rank's create fails at once (it never joins), or
-  // its init never settles (the bounded wait runs out: PM_ETIMEDOUT after limit)
-  static const int fault = [] { const char* e = getenv("PM_FAULT_RCCL_CREATE"); return e ? atoi(e) : -1; }();
-  static const int fault_block = [] { const char* e = getenv("PM_FAULT_RCCL_BLOCK"); return e ? atoi(e) : -1; }();
-  if (fault == rank) return fail(PM_EHIP, "injected fault (PM_FAULT_RCCL_CREATE)");
-  if (fault_block == rank) {
-    const auto t0 = Clock::now();
-    while (std::chrono::duration<double>(Clock::now() - t0).count() <= limit)
-      std::this_thread::sleep_for(std::chrono::milliseconds(5));
-    return fail(PM_ETIMEDOUT, "RCCL communicators not ready after " + std::to_string((int)limit) +
-                                  " s (injected: PM_FAULT_RCCL_BLOCK)");
-  }
-  const RcclApi& a = rccl_api();
-  if (!a.err.empty()) return fail(PM_EHIP, "RCCL unavailable: " + a.err);
-  if (!a.nonblocking()) return fail(PM_EHIP, "RCCL lacks the nonblocking init (ncclCommInitRankConfig / ncclCommAbort)");
-  HIPCHK(hipSetDevice(device));
-  std::unique_ptr<pm_rccl> r(new pm_rccl());
-  r->device = device; r->nranks = nranks; r->rank = rank;
-  r->comms.assign(nteams, nullptr);
-  r->nonblocking = true;
-  if (rccl_debug()) fprintf(stderr, "[pm] rccl_create rank %d/%d teams %u (grouped nonblocking inits)\n", rank, nranks, nteams);
-  // every rank issues the teams' inits in the same order, as one group
-  ncclResult_t gres = a.group_start();
-  for (uint32_t t = 0; t < nteams && (gres == ncclSuccess || gres == ncclInProgress); ++t) {
-    ncclUniqueId u;
-    memcpy(&u, ids + (size_t)t * PM_RCCL_ID_BYTES, sizeof u);
-    ncclConfig_t cfg = NCCL_CONFIG_INITIALIZER;
-    cfg.blocking = 0;
-    gres = a.comm_init_rank_config(&r->comms[t], nranks, u, rank, &cfg);
-  }
-  const ncclResult_t eres = a.group_end();
-  if (rccl_debug()) fprintf(stderr, "[pm] rccl_create: group end %d (%s)\n", (int)eres, a.error_string(eres));
-  if ((gres != ncclSuccess && gres != ncclInProgress) || (eres != ncclSuccess && eres != ncclInProgress)) {
-    r->abort_all();
-    return fail(PM_EHIP, std::string("ncclCommInitRankConfig: ") +
-                             a.error_string(gres != ncclSuccess && gres != ncclInProgress ? gres : eres));
-  }
-  const auto t0 = Clock::now();
-  for (uint32_t t = 0; t < nteams; ++t) {
-    const double left = limit - std::chrono::duration<double>(Clock::now() - t0).count();
-    const ncclResult_t st = rccl_settle(r.get(), r->comms[t], ncclInProgress, std::max(0.0, left));
-    if (st == ncclInProgress) {
-      r->abort_all();
-      return fail(PM_ETIMEDOUT, "RCCL communicator " + std::to_string(t) + " not ready after " +
-                                    std::to_string((int)limit) + " s (a peer rank did not join)");
-    }
-    if (st != ncclSuccess) {
-      r->abort_all();
-      return fail(PM_EHIP, std::string("RCCL communicator init: ") + a.error_string(st));
-    }
-  }
-  if (rccl_debug())
-    fprintf(stderr, "[pm] rccl_create: %u communicators ready in %.3f s\n", nteams,
-            std::chrono::duration<double>(Clock::now() - t0).count());
-  *out = r.release();
-  return 0;
-}
-
-extern "C" void pm_rccl_destroy(pm_rccl* r) {
-  if (!r) return;
-  (void)hipSetDevice(r->device);
-  delete r;
-}
-
-extern "C" int pm_rccl_combine(void* user, uint32_t team, uint64_t* dev_words, uint64_t nwords, void* stream) {
-  pm_rccl* r = (pm_rccl*)user;
-  if (!r || r->comms.empty() || !dev_words) return fail(PM_EINVAL, "bad argument");
-  if (r->aborted) return fail(PM_EHIP, "RCCL communicators were aborted");
-  // in place, on the team's stream: ordered after the records' pack and before their read-back
-  ncclComm_t c = r->comms[team % r->comms.size()];
-  const ncclResult_t res = rccl_settle(r, c, rccl_api().all_reduce(dev_words, dev_words, nwords, ncclUint64, ncclSum, c,
-                                                                   (hipStream_t)stream), rccl_timeout_s());
-  if (res == ncclInProgress) return fail(PM_ETIMEDOUT, "ncclAllReduce not issued within the RCCL timeout");
-  if (res != ncclSuccess) return fail(PM_EHIP, std::string("ncclAllReduce: ") + rccl_api().error_string(res));
-  return 0;
-}
-
-// One 1-word all-reduce per team over the fresh communicators, on a private
-// stream, completed within rccl_timeout_s(): every rank must see the sum
-// nranks.  On a timeout or a wrong sum the communicators are aborted (their
-// kernels return) and the handle refuses further combines.  Callers agree on
-// the outcome over another channel (a MIN of the ranks' flags) before use.
-extern "C" int pm_rccl_probe(pm_rccl* r) {
-  if (!r || r->comms.empty()) return fail(PM_EINVAL, "bad argument");
-  if (r->aborted) return fail(PM_EHIP, "RCCL communicators were aborted");
-  HIPCHK(hipSetDevice(r->device));
-  const uint32_t nt = (uint32_t)r->comms.size();
-  DevBuf buf;
-  CHK(buf.reserve(nt * 8));
-  std::vector<uint64_t> one(nt, 1), got(nt, 0);
-  hipStream_t st = nullptr;
-  HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  struct Stream { hipStream_t s; ~Stream() { (void)hipStreamDestroy(s); } } guard{st};
-  HIPCHK(hipMemcpyAsync(buf.p, one.data(), nt * 8, hipMemcpyHostToDevice, st));
-  const double limit = rccl_timeout_s();
-  if (rccl_debug()) fprintf(stderr, "[pm] rccl_probe: %u teams\n", nt);
-  for (uint32_t t = 0; t < nt; ++t) {
-    const int rc = pm_rccl_combine(r, t, buf.as<uint64_t>() + t, 1, st);
-    if (rc) { r->abort_all(); return rc; }
-  }
-  if (rccl_debug()) fprintf(stderr, "[pm] rccl_probe: all-reduces issued\n");
-  const auto t0 = Clock::now();
-  for (;;) {
-    const hipError_t e = hipStreamQuery(st);
-    if (e == hipSuccess) break;
-    if (e != hipErrorNotReady) { r->abort_all(); return fail(PM_EHIP, std::string("RCCL probe: ") + hipGetErrorString(e)); }
-    if (std::chrono::duration<double>(Clock::now() - t0).count() > limit) {
-      r->abort_all();
-      (void)hipStreamSynchronize(st);   // the aborted communicators' kernels return
-      return fail(PM_ETIMEDOUT, "RCCL probe all-reduce not complete after " + std::to_string((int)limit) + " s");
-    }
-    std::this_thread::sleep_for(std::chrono::microseconds(50));
-  }
-  HIPCHK(hipMemcpy(got.data(), buf.p, nt * 8, hipMemcpyDeviceToHost));
-  for (uint32_t t = 0; t < nt; ++t)
-    if (got[t] != (uint64_t)r->nranks) {
-      r->abort_all();
-      return fail(PM_EHIP, "RCCL probe: team " + std::to_string(t) + " summed " + std::to_string(got[t]) + ", want " +
-                               std::to_string(r->nranks));
-    }
-  return 0;
-}
-
 // Words of one team's records in pm_search_loop_sharded: sessions x (parallel
 // x m) ids x W, W = the row words holding the neighbour list + 1.
 extern "C" uint64_t pm_sharded_record_words(pm_graph* g, uint32_t sessions, int parallel) {
@@ -4912,262 +4184,6 @@ extern "C" int pm_search_loop_sharded(pm_graph** gs, uint32_t S, const float* qu
   for (uint32_t s = 0; s < S; ++s) {
     if (online_s) online_s[s] = wall - mt[s];
     if (maint_s) maint_s[s] = mt[s];
-  }
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
-// Graph construction and exact kNN ground truth.
-// CreateGraphBasedOnNGT (graphann/build_graph.go:314-523) with the NGT
-// candidate search replaced by exact kNN: GPU bf16 MFMA prefilter (top 64) and
-// an exact re-rank in L2Dist order (pm_graph.hip); robustPrune on the GPU;
-// reverse edges, sampling and the random fill on host threads (O(n m)).
-// Randomness (the reference's per-thread math/rand, :455,473-475) comes from
-// hash4 domains 7 (edge sampling) and 8 (fill), so any thread split gives the
-// same graph.  oracle/pm_oracle.cpp (or_build_graph) restates the same spec.
-// ---------------------------------------------------------------------------
-enum : uint64_t { DOM_GRAPH_SAMPLE = 7, DOM_GRAPH_FILL = 8 };
-
-template <class F> static void par_for(uint64_t n, F&& f) {
-  const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  if (n < 4096 || nt == 1) { f(0, n); return; }
-  std::vector<std::thread> th;
-  const uint64_t per = (n + nt - 1) / nt;
-  for (unsigned t = 0; t < nt; ++t) {
-    const uint64_t a = t * per, b = std::min(n, a + per);
-    if (a < b) th.emplace_back([&, a, b] { f(a, b); });
-  }
-  for (auto& t : th) t.join();
-}
-
-struct KnnDev {   // device copies for the prefilter + re-rank
-  DevBuf x, xb, xn;
-  uint32_t dp = 0;
-};
-static int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDev& d) {
-  d.dp = pmk::knn_pad_dim(dim);
-  if (!d.dp) return fail(PM_EINVAL, "kNN supports dim <= 192");
-  CHK(d.x.reserve(std::max<uint64_t>(4, n * dim * 4)));
-  CHK(d.xb.reserve(std::max<uint64_t>(4, n * d.dp * 2)));
-  CHK(d.xn.reserve(std::max<uint64_t>(4, n * 4)));
-  HIPCHK(hipMemcpyAsync(d.x.p, v, n * dim * 4, hipMemcpyHostToDevice, c->stream));
-  c->timed("to_bf16", (double)n * dim * 4, [&] { pmk::to_bf16(c->stream, d.x.as<float>(), n, dim, d.dp, d.xb.p, d.xn.as<float>()); });
-  return 0;
-}
-
-// Exact k nearest base rows of each query by (L2Dist, id), k <= 64 (the
-// ground truth of ComputeRecall, build_graph.go:821-863); ids -1 padded.
-extern "C" int pm_knn(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
-                      uint32_t k, int64_t* ids, float* dists) {
-  if (!c || !base || (!queries && nq) || (!ids && nq)) return fail(PM_EINVAL, "NULL argument");
-  if (k == 0 || k > pmk::knn_top()) return fail(PM_EINVAL, "k must be in [1, 64]");
-  if (n == 0 || dim == 0 || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be in [1, 2^32-1)");
-  HIPCHK(hipSetDevice(c->device));
-  KnnDev B, Q;
-  CHK(knn_upload(c, base, n, (uint32_t)dim, B));
-  CHK(knn_upload(c, queries, nq, (uint32_t)dim, Q));
-  DevBuf cand, out, dist, len;
-  CHK(cand.reserve(std::max<uint64_t>(4, nq * pmk::knn_top() * 4)));
-  CHK(out.reserve(std::max<uint64_t>(4, nq * k * 4)));
-  CHK(dist.reserve(std::max<uint64_t>(4, nq * k * 4)));
-  CHK(len.reserve(std::max<uint64_t>(4, nq * 4)));
-  c->timed("knn_prefilter", (double)nq * n * B.dp * 2, [&] {
-    pmk::knn_prefilter(c->stream, B.xb.p, B.xn.as<float>(), n, Q.xb.p, Q.xn.as<float>(), nq, B.dp, cand.as<uint32_t>()); });
-  c->timed("knn_rerank", (double)nq * pmk::knn_top() * dim * 4, [&] {
-    pmk::knn_rerank(c->stream, B.x.as<float>(), n, (uint32_t)dim, Q.x.as<float>(), nq, cand.as<uint32_t>(), k, false,
-                    out.as<uint32_t>(), dist.as<float>(), len.as<uint32_t>()); });
-  std::vector<uint32_t> o(nq * k), l(nq);
-  std::vector<float> dd(nq * k);
-  HIPCHK(hipMemcpyAsync(o.data(), out.p, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(dd.data(), dist.p, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(l.data(), len.p, nq * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  for (uint64_t i = 0; i < nq; ++i)
-    for (uint32_t j = 0; j < k; ++j) {
-      ids[i * k + j] = j < l[i] ? (int64_t)o[i * k + j] : -1;
-      if (dists) dists[i * k + j] = j < l[i] ? dd[i * k + j] : INFINITY;
-    }
-  return 0;
-}
-
-extern "C" int pm_build_graph(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
-                              uint64_t seed, uint32_t* graph, double* times) {
-  if (!c || !vectors || !graph) return fail(PM_EINVAL, "NULL argument");
-  const uint32_t K = (uint32_t)((float)m * 1.5f);   // int(float32(m)*1.5) NGT results (build_graph.go:398)
-  if (m == 0 || m > pmk::prune_max_m() || K + 1 > pmk::knn_top())
-    return fail(PM_EINVAL, "m must be in [1, 42] (1.5 m candidates + self within the 64-key prefilter)");
-  if (dim == 0 || dim > pmk::prune_max_dim() || !pmk::knn_pad_dim((uint32_t)dim))
-    return fail(PM_EINVAL, "dim must be in [1, 192]");
-  if (n <= m || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be > m (the random fill needs m other vertices)");
-  HIPCHK(hipSetDevice(c->device));
-  hipStream_t st = c->stream;
-  auto t0 = Clock::now();
-  KnnDev X;
-  CHK(knn_upload(c, vectors, n, (uint32_t)dim, X));
-  DevBuf cand, ck, clen, g1, len1, err;
-  CHK(cand.reserve(n * pmk::knn_top() * 4));
-  CHK(ck.reserve(n * K * 4));
-  CHK(clen.reserve(n * 4));
-  CHK(g1.reserve(n * m * 4));
-  CHK(len1.reserve(n * 4));
-  CHK(err.reserve(4));
-  HIPCHK(hipMemsetAsync(err.p, 0, 4, st));
-  // candidates: NGT.Search(u, 1.5m) with u removed (:398-410), exact here
-  c->timed("knn_prefilter", (double)n * n * X.dp * 2, [&] {
-    pmk::knn_prefilter(st, X.xb.p, X.xn.as<float>(), n, X.xb.p, X.xn.as<float>(), n, X.dp, cand.as<uint32_t>()); });
-  c->timed("knn_rerank", (double)n * pmk::knn_top() * dim * 4, [&] {
-    pmk::knn_rerank(st, X.x.as<float>(), n, (uint32_t)dim, X.x.as<float>(), n, cand.as<uint32_t>(), K, true,
-                    ck.as<uint32_t>(), nullptr, clen.as<uint32_t>()); });
-  HIPCHK(hipStreamSynchronize(st));
-  auto t1 = Clock::now();
-  // first pass: robustPrune(vectors, u, candidates, m, alpha) (:413-414)
-  c->timed("prune", 0.0, [&] {
-    pmk::prune(st, X.x.as<float>(), (uint32_t)dim, nullptr, n, nullptr, K, clen.as<uint32_t>(), ck.as<uint32_t>(),
-               (uint32_t)m, alpha, g1.as<uint32_t>(), len1.as<uint32_t>(), err.as<uint32_t>()); });
-  std::vector<uint32_t> G(n * m), L1(n);
-  uint32_t e = 0;
-  HIPCHK(hipMemcpyAsync(G.data(), g1.p, n * m * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(L1.data(), len1.p, n * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipMemcpyAsync(&e, err.p, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  if (e) return fail(PM_EINVAL, "robustPrune: candidate list above the kernel's limit");
-  auto t2 = Clock::now();
-  // bi-directional edges (:421-430): biGraph[x] = [u < x with x in graph[u]] ++
-  // graph[x] ++ [u > x with x in graph[u]], u ascending, with multiplicity
-  std::vector<uint64_t> roff(n + 1, 0);
-  for (uint64_t u = 0; u < n; ++u)
-    for (uint32_t j = 0; j < L1[u]; ++j) roff[G[u * m + j] + 1]++;
-  for (uint64_t x = 0; x < n; ++x) roff[x + 1] += roff[x];
-  std::vector<uint32_t> rev(roff[n]);
-  {
-    std::vector<uint64_t> fillp(roff.begin(), roff.end() - 1);
-    for (uint64_t u = 0; u < n; ++u)
-      for (uint32_t j = 0; j < L1[u]; ++j) rev[fillp[G[u * m + j]]++] = (uint32_t)u;
-  }
-  std::vector<uint32_t> inb(n);   // inbounds = len(biGraph) (:433-436)
-  for (uint64_t x = 0; x < n; ++x) inb[x] = (uint32_t)(L1[x] + roff[x + 1] - roff[x]);
-  // sampling (:448-462): keep edge j of u with probability min(1.5m / inbounds[v], 1)
-  std::vector<uint32_t> clen2(n);
-  std::vector<uint64_t> coff(n + 1, 0);
-  auto visit = [&](uint64_t x, auto&& fn) {   // biGraph[x] in order
-    const uint32_t* r = rev.data() + roff[x];
-    const uint64_t nr = roff[x + 1] - roff[x];
-    uint64_t a = 0, j = 0;
-    while (a < nr && r[a] < x) fn(j++, r[a++]);
-    for (uint32_t i = 0; i < L1[x]; ++i) fn(j++, G[x * m + i]);
-    while (a < nr) fn(j++, r[a++]);
-  };
-  auto keep = [&](uint64_t u, uint64_t j, uint32_t v) {
-    const double prob = std::min(1.5 * (double)m / (double)inb[v], 1.0);
-    const double r = (double)(hash4(seed, DOM_GRAPH_SAMPLE, u, j, 0) >> 11) * 0x1.0p-53;
-    return r < prob;
-  };
-  par_for(n, [&](uint64_t a, uint64_t b) {
-    for (uint64_t u = a; u < b; ++u) {
-      uint32_t cnt = 0;
-      visit(u, [&](uint64_t j, uint32_t v) { cnt += keep(u, j, v); });
-      clen2[u] = cnt;
-    }
-  });
-  for (uint64_t u = 0; u < n; ++u) coff[u + 1] = coff[u] + clen2[u];
-  std::vector<uint32_t> conn(coff[n]);
-  par_for(n, [&](uint64_t a, uint64_t b) {
-    for (uint64_t u = a; u < b; ++u) {
-      uint32_t* o = conn.data() + coff[u];
-      visit(u, [&](uint64_t j, uint32_t v) { if (keep(u, j, v)) *o++ = v; });
-    }
-  });
-  // second pass: robustPrune of the lists above m (:464-466) on the GPU.  Lists
-  // above the kernel's LDS sort (hub vertices: every in-edge of a popular
-  // vertex is kept, :448-462 sample by the TARGET's inbounds) get their
-  // candidate distances on the GPU, their (L2Dist, position) order by a host
-  // sort of those exact keys, and the same greedy pass (presorted k_prune).
-  std::vector<uint32_t> big, huge;
-  for (uint64_t u = 0; u < n; ++u)
-    if (clen2[u] > pmk::prune_max_list()) huge.push_back((uint32_t)u);
-    else if (clen2[u] > m) big.push_back((uint32_t)u);
-  auto t3 = Clock::now();
-  if (!big.empty() || !huge.empty()) {
-    DevBuf dv, dh, doff, dlen, dids, dout, dol, dd, dpos;
-    CHK(dv.reserve(std::max<size_t>(1, big.size()) * 4));
-    CHK(dh.reserve(std::max<size_t>(1, huge.size()) * 4));
-    CHK(doff.reserve(n * 8));
-    CHK(dlen.reserve(n * 4));
-    CHK(dids.reserve(std::max<uint64_t>(4, conn.size() * 4)));
-    CHK(dout.reserve(n * m * 4));
-    CHK(dol.reserve(n * 4));
-    if (!big.empty()) HIPCHK(hipMemcpyAsync(dv.p, big.data(), big.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(doff.p, coff.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dlen.p, clen2.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dids.p, conn.data(), conn.size() * 4, hipMemcpyHostToDevice, st));
-    c->timed("prune", 0.0, [&] {
-      pmk::prune(st, X.x.as<float>(), (uint32_t)dim, dv.as<uint32_t>(), big.size(), doff.as<uint64_t>(), 0,
-                 dlen.as<uint32_t>(), dids.as<uint32_t>(), (uint32_t)m, alpha, dout.as<uint32_t>(),
-                 dol.as<uint32_t>(), err.as<uint32_t>()); });
-    if (!huge.empty()) {
-      CHK(dd.reserve(conn.size() * 4));
-      CHK(dpos.reserve(conn.size() * 4));
-      HIPCHK(hipMemcpyAsync(dh.p, huge.data(), huge.size() * 4, hipMemcpyHostToDevice, st));
-      pmk::cand_dist(st, X.x.as<float>(), (uint32_t)dim, dh.as<uint32_t>(), huge.size(), doff.as<uint64_t>(),
-                     dlen.as<uint32_t>(), dids.as<uint32_t>(), dd.as<float>());
-      std::vector<float> hd(conn.size());
-      HIPCHK(hipMemcpyAsync(hd.data(), dd.p, conn.size() * 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      std::vector<uint32_t> pos(conn.size());
-      par_for(huge.size(), [&](uint64_t a, uint64_t b) {
-        std::vector<uint64_t> key;
-        for (uint64_t i = a; i < b; ++i) {   // sort.Slice by distance; ties by position (as the LDS sort)
-          const uint32_t u = huge[i];
-          const uint64_t o = coff[u], len = clen2[u];
-          key.resize(len);
-          for (uint64_t j = 0; j < len; ++j) {
-            uint32_t bits;
-            memcpy(&bits, &hd[o + j], 4);
-            key[j] = ((uint64_t)bits << 32) | j;
-          }
-          std::sort(key.begin(), key.end());
-          for (uint64_t j = 0; j < len; ++j) pos[o + j] = (uint32_t)key[j];
-        }
-      });
-      HIPCHK(hipMemcpyAsync(dpos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, st));
-      c->timed("prune", 0.0, [&] {
-        pmk::prune(st, X.x.as<float>(), (uint32_t)dim, dh.as<uint32_t>(), huge.size(), doff.as<uint64_t>(), 0,
-                   dlen.as<uint32_t>(), dids.as<uint32_t>(), (uint32_t)m, alpha, dout.as<uint32_t>(),
-                   dol.as<uint32_t>(), err.as<uint32_t>(), dpos.as<uint32_t>(), dd.as<float>()); });
-    }
-    std::vector<uint32_t> P(n * m), PL(n);
-    HIPCHK(hipMemcpyAsync(P.data(), dout.p, n * m * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(PL.data(), dol.p, n * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&e, err.p, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (e) return fail(PM_EINVAL, "robustPrune: a connection list above the kernel's limit");
-    for (const auto* lst : {&big, &huge})
-      for (uint32_t u : *lst) {   // robustPrune of a list > m returns exactly m
-        memcpy(conn.data() + coff[u], &P[(uint64_t)u * m], m * 4);
-        clen2[u] = PL[u];
-      }
-  }
-  auto t4 = Clock::now();
-  // random fill to exactly m (:468-486)
-  par_for(n, [&](uint64_t a, uint64_t b) {
-    std::vector<uint32_t> cur;
-    for (uint64_t u = a; u < b; ++u) {
-      cur.assign(conn.data() + coff[u], conn.data() + coff[u] + std::min<uint64_t>(clen2[u], m));
-      uint64_t t = 0;
-      while (cur.size() < m) {
-        const uint32_t v = (uint32_t)(hash4(seed, DOM_GRAPH_FILL, u, t++, 0) % n);
-        if (v == u) continue;
-        if (std::find(cur.begin(), cur.end(), v) != cur.end()) continue;
-        cur.push_back(v);
-      }
-      memcpy(graph + u * m, cur.data(), m * 4);
-    }
-  });
-  if (times) {
-    times[0] = std::chrono::duration<double>(t1 - t0).count();   // kNN candidates
-    times[1] = std::chrono::duration<double>(t2 - t1).count();   // first robustPrune
-    times[2] = std::chrono::duration<double>(t3 - t2 + (Clock::now() - t4)).count();   // host edges, sampling, fill
-    times[3] = std::chrono::duration<double>(t4 - t3).count();   // second robustPrune
   }
   return 0;
 }

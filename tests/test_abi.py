@@ -42,6 +42,35 @@ def test_host_key_schedule_matches_oracle(oracle):
         assert np.array_equal(pm.expand_key(k), oracle.expand_key(k))
 
 
+def test_last_error_crosses_files():
+    """One argument-checked entry point of every layer of the host side (the
+    csrc/pm_*.cpp files, and the layers pm_engine.cpp still holds together):
+    each fails with PM_EINVAL before any HIP call, and pm_last_error, which
+    lives in pm_ctx.cpp, returns that call's text: the error text is one per
+    thread, not one per file."""
+    import pacmann_amd as pm
+    L = pm.lib()
+    PM_EINVAL = -1   # include/pacmann.h
+    out = C.c_void_p()
+    cases = [
+        ("context", lambda: L.pm_ctx_create(0, None), b"out is NULL"),
+        ("engine", lambda: L.pm_pir_create(None, 16, 8, None, 8, 1, None), b"out is NULL"),
+        ("search", lambda: L.pm_graph_create(None, 1, 1, 1, None, None, 0, 0, 1, 1, C.byref(out)),
+         b"NULL argument"),
+        ("group", lambda: L.pm_batchpir_group_create(None, 0, None), b"NULL argument"),
+        ("device loop", lambda: L.pm_search_loop_batched(None, 0, None, 0, 1, 1, 1, 1, 1, None, None, None, None),
+         b"NULL argument"),
+        ("rccl", lambda: L.pm_rccl_create(0, 1, 0, None, 1, C.byref(out)), b"bad argument"),
+        ("graph build", lambda: L.pm_knn(None, None, 1, 1, None, 0, 1, None, None), b"NULL argument"),
+    ]
+    for layer, call, want in cases:
+        # another text first (set in pm_ctx.cpp), so that an equal text of the case before cannot pass for this one
+        assert L.pm_ctx_mem_info(None, None, None) == PM_EINVAL
+        assert L.pm_last_error() == b"ctx is NULL"
+        assert call() == PM_EINVAL, layer
+        assert L.pm_last_error() == want, layer
+
+
 def test_no_gpu_raises_loudly():
     """Without a HIP device the product must fail, never fall back to CPU."""
     import pacmann_amd as pm
