@@ -421,9 +421,21 @@ int pm_search_loop_sharded(pm_graph** sessions, uint32_t S, const float* queries
  * ground truth ComputeRecall (build_graph.go:821-863) scores against.  ids:
  * nq x k (-1 padded), dists: nq x k or NULL.  Exact for integer-valued rows
  * (e.g. SIFT's uint8 values); for general float rows the GPU keeps the 64 best
- * by bf16-rounded distance before the exact re-rank. */
+ * by bf16-rounded distance before the exact re-rank, so the result can differ
+ * from brute force: pm_knn_exact is exact for those too. */
 int pm_knn(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
            uint32_t k, int64_t* ids, float* dists);
+/* pm_knn, exact for every finite float input: the result is the brute-force
+ * (L2Dist in l2_distance_amd64.s order, id) ranking.  The prefilter splits
+ * every row into two bf16 halves and bounds its own error (eps <= 2^-12 (|q|^2 +
+ * max |x|^2)); a query row whose k-th exact distance lies more
+ * than eps below the prefilter distance of its 64th candidate is certified,
+ * every other row is answered again by a brute-force kernel (slow: n dim
+ * operations per row).  *fallback_rows (nullable): rows answered by the
+ * brute-force kernel instead of the certified prefilter.  Non-finite inputs
+ * get some answer through the fallback.  Arguments as pm_knn; dim <= 192. */
+int pm_knn_exact(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                 uint32_t k, int64_t* ids, float* dists, uint64_t* fallback_rows);
 /* BuildGraph / CreateGraphBasedOnNGT (build_graph.go:97-105,314-523) with the
  * NGT candidate search (absent here) replaced by exact kNN: candidates =
  * int(1.5 m) nearest by (L2Dist, id) minus u; robustPrune (alpha); reverse
@@ -434,6 +446,11 @@ int pm_knn(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, const float
  * dim <= 192, m <= 42. */
 int pm_build_graph(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
                    uint64_t seed, uint32_t* graph, double* times);
+/* pm_build_graph with pm_knn_exact's candidates: equals the oracle's graph for
+ * float rows too.  *fallback_rows (nullable): vertices whose candidates came
+ * from the brute-force kernel.  Other arguments as pm_build_graph. */
+int pm_build_graph_exact(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
+                         uint64_t seed, uint32_t* graph, double* times, uint64_t* fallback_rows);
 
 #ifdef __cplusplus
 }

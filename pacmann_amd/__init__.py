@@ -115,6 +115,8 @@ SIGNATURES = {
     "pm_graph_create_session": (C.c_int, [vp, vp, u64, u64, C.POINTER(vp)]),
     "pm_knn": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, i64p, f32p]),
     "pm_build_graph": (C.c_int, [vp, f32p, u64, u64, u64, C.c_float, u64, u32p, C.POINTER(dbl)]),
+    "pm_knn_exact": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, i64p, f32p, u64p]),
+    "pm_build_graph_exact": (C.c_int, [vp, f32p, u64, u64, u64, C.c_float, u64, u32p, C.POINTER(dbl), u64p]),
     "pm_search_loop_sessions": (C.c_int, [C.POINTER(vp), C.c_uint32, f32p, u64, C.c_int, C.c_int, C.c_int,
                                           i64p, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "pm_batchpir_group_create": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
@@ -847,15 +849,41 @@ def knn(base, queries, k: int, ctx: Context | None = None, with_dist: bool = Fal
     return (ids, d) if with_dist else ids
 
 
-def build_graph(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context | None = None):
+def knn_exact(base, queries, k: int, ctx: Context | None = None, with_dist: bool = False):
+    """pm.knn, exact for every finite float input (pm_knn_exact).  Returns
+    (ids[, dists], fallback_rows): fallback_rows query rows were answered by the
+    brute-force kernel because the prefilter's certificate did not hold."""
+    ctx = ctx or default_context()
+    b = np.ascontiguousarray(base, dtype=np.float32)
+    q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, b.shape[1])
+    ids = np.zeros((q.shape[0], k), dtype=np.int64)
+    d = np.zeros((q.shape[0], k), dtype=np.float32)
+    fb = u64(0)
+    _check(lib().pm_knn_exact(ctx.h, _p(b, f32p), b.shape[0], b.shape[1], _p(q, f32p), q.shape[0], k, _p(ids, i64p),
+                              _p(d, f32p), C.byref(fb)))
+    return (ids, d, int(fb.value)) if with_dist else (ids, int(fb.value))
+
+
+def build_graph(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context | None = None,
+                exact: bool = False):
     """graphann.BuildGraph (build_graph.go:97-105,314-523) on the GPU with exact
-    kNN candidates (pm_build_graph).  Returns (graph [n, m] uint32, times dict)."""
+    kNN candidates (pm_build_graph).  Returns (graph [n, m] uint32, times dict).
+    exact=True: pm_build_graph_exact, whose candidates are exact for general
+    float rows too; times then has "knn_fallback_rows"."""
     ctx = ctx or default_context()
     v = np.ascontiguousarray(vectors, dtype=np.float32)
     g = np.zeros((v.shape[0], m), dtype=np.uint32)
     t = (dbl * 4)()
-    _check(lib().pm_build_graph(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], m, alpha, seed, _p(g, u32p), t))
-    return g, {"knn_s": t[0], "prune1_s": t[1], "host_edges_s": t[2], "prune2_s": t[3]}
+    fb = u64(0)
+    if exact:
+        _check(lib().pm_build_graph_exact(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], m, alpha, seed, _p(g, u32p), t,
+                                          C.byref(fb)))
+    else:
+        _check(lib().pm_build_graph(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], m, alpha, seed, _p(g, u32p), t))
+    times = {"knn_s": t[0], "prune1_s": t[1], "host_edges_s": t[2], "prune2_s": t[3]}
+    if exact:
+        times["knn_fallback_rows"] = int(fb.value)
+    return g, times
 
 
 GraphANNFrontend = PIRGraphInfo

@@ -27,57 +27,117 @@ template <class F> static void par_for(uint64_t n, F&& f) {
 }
 
 struct KnnDev {   // device copies for the prefilter + re-rank
-  DevBuf x, xb, xn;
+  DevBuf x, xb, xl, xn, mx;   // f32 rows, bf16 rows (exact: hi), exact: lo, norms, exact: the largest norm's bits
   uint32_t dp = 0;
 };
-static int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDev& d) {
+// exact: the split rows of pm_knn_exact (hi + lo, norms of the f32 values)
+static int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDev& d, bool exact) {
   d.dp = pmk::knn_pad_dim(dim);
   if (!d.dp) return fail(PM_EINVAL, "kNN supports dim <= 192");
   CHK(d.x.reserve(std::max<uint64_t>(4, n * dim * 4)));
   CHK(d.xb.reserve(std::max<uint64_t>(4, n * d.dp * 2)));
   CHK(d.xn.reserve(std::max<uint64_t>(4, n * 4)));
   HIPCHK(hipMemcpyAsync(d.x.p, v, n * dim * 4, hipMemcpyHostToDevice, c->stream));
-  c->timed("to_bf16", (double)n * dim * 4, [&] { pmk::to_bf16(c->stream, d.x.as<float>(), n, dim, d.dp, d.xb.p, d.xn.as<float>()); });
+  if (!exact) {
+    c->timed("to_bf16", (double)n * dim * 4, [&] { pmk::to_bf16(c->stream, d.x.as<float>(), n, dim, d.dp, d.xb.p, d.xn.as<float>()); });
+    return 0;
+  }
+  CHK(d.xl.reserve(std::max<uint64_t>(4, n * d.dp * 2)));
+  CHK(d.mx.reserve(4));
+  HIPCHK(hipMemsetAsync(d.mx.p, 0, 4, c->stream));
+  c->timed("to_bf16", (double)n * dim * 4, [&] {
+    pmk::to_bf16x2(c->stream, d.x.as<float>(), n, dim, d.dp, d.xb.p, d.xl.p, d.xn.as<float>(), d.mx.as<uint32_t>()); });
   return 0;
 }
 
-// Exact k nearest base rows of each query by (L2Dist, id), k <= 64 (the
-// ground truth of ComputeRecall, build_graph.go:821-863); ids -1 padded.
-extern "C" int pm_knn(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
-                      uint32_t k, int64_t* ids, float* dists) {
+// The first K of every query row's (L2Dist, id) ranking of the base rows, self
+// dropped when self_base (Q is B): out [nq][K] with len [nq] valid entries each,
+// dist [nq][K] when want_dist.  Prefilter (64 candidates per row) and exact
+// re-rank; exact: the three-product prefilter, the certificate in the re-rank
+// and the brute-force pass over the rows it did not certify, whose number goes
+// to *fallback (pm_knn_exact).  Enqueued on c->stream; exact synchronises it.
+struct KnnOut { DevBuf cand, out, dist, len; };
+static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, uint64_t nq, uint32_t dim, uint32_t K,
+                      bool self_base, bool want_dist, bool exact, KnnOut& o, uint64_t* fallback) {
+  hipStream_t st = c->stream;
+  CHK(o.cand.reserve(std::max<uint64_t>(4, nq * pmk::knn_top() * 4)));
+  CHK(o.out.reserve(std::max<uint64_t>(4, nq * K * 4)));
+  if (want_dist) CHK(o.dist.reserve(std::max<uint64_t>(4, nq * K * 4)));
+  CHK(o.len.reserve(std::max<uint64_t>(4, nq * 4)));
+  const double pre_bytes = (double)nq * n * B.dp * 2, rr_bytes = (double)nq * pmk::knn_top() * dim * 4;
+  if (!exact) {
+    c->timed("knn_prefilter", pre_bytes, [&] {
+      pmk::knn_prefilter(st, B.xb.p, B.xn.as<float>(), n, Q.xb.p, Q.xn.as<float>(), nq, B.dp, o.cand.as<uint32_t>()); });
+    c->timed("knn_rerank", rr_bytes, [&] {
+      pmk::knn_rerank(st, B.x.as<float>(), n, dim, Q.x.as<float>(), nq, o.cand.as<uint32_t>(), K, self_base,
+                      o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>()); });
+    return 0;
+  }
+  DevBuf tau, list, nlist;
+  CHK(tau.reserve(std::max<uint64_t>(4, nq * 4)));
+  CHK(list.reserve(std::max<uint64_t>(8, nq * 8)));
+  CHK(nlist.reserve(8));
+  HIPCHK(hipMemsetAsync(nlist.p, 0, 8, st));
+  c->timed("knn_prefilter_x3", 2 * pre_bytes, [&] {
+    pmk::knn_prefilter_x3(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
+                          o.cand.as<uint32_t>(), tau.as<float>()); });
+  c->timed("knn_rerank", rr_bytes, [&] {
+    pmk::knn_rerank_cert(st, B.x.as<float>(), n, dim, Q.x.as<float>(), nq, o.cand.as<uint32_t>(), K, self_base,
+                         o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>(), Q.xn.as<float>(),
+                         tau.as<float>(), B.mx.as<uint32_t>(), B.dp, list.as<uint64_t>(), nlist.as<uint64_t>()); });
+  uint64_t nl = 0;
+  HIPCHK(hipMemcpyAsync(&nl, nlist.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  c->timed("knn_brute", (double)nl * n * dim * 4, [&] {
+    pmk::knn_brute(st, B.x.as<float>(), n, dim, Q.x.as<float>(), list.as<uint64_t>(), nl, K, self_base,
+                   o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>()); });
+  HIPCHK(hipStreamSynchronize(st));   // list and tau are freed on return
+  if (fallback) *fallback = nl;
+  return 0;
+}
+
+// pm_knn and pm_knn_exact: exact k nearest base rows of each query by (L2Dist,
+// id), k <= 64 (the ground truth of ComputeRecall, build_graph.go:821-863);
+// ids -1 padded.
+static int knn_impl(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                    uint32_t k, int64_t* ids, float* dists, bool exact, uint64_t* fallback) {
   if (!c || !base || (!queries && nq) || (!ids && nq)) return fail(PM_EINVAL, "NULL argument");
   if (k == 0 || k > pmk::knn_top()) return fail(PM_EINVAL, "k must be in [1, 64]");
   if (n == 0 || dim == 0 || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be in [1, 2^32-1)");
+  if (exact && !pmk::knn_pad_dim((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)))
+    return fail(PM_EINVAL, "kNN supports dim <= 192");
   HIPCHK(hipSetDevice(c->device));
   KnnDev B, Q;
-  CHK(knn_upload(c, base, n, (uint32_t)dim, B));
-  CHK(knn_upload(c, queries, nq, (uint32_t)dim, Q));
-  DevBuf cand, out, dist, len;
-  CHK(cand.reserve(std::max<uint64_t>(4, nq * pmk::knn_top() * 4)));
-  CHK(out.reserve(std::max<uint64_t>(4, nq * k * 4)));
-  CHK(dist.reserve(std::max<uint64_t>(4, nq * k * 4)));
-  CHK(len.reserve(std::max<uint64_t>(4, nq * 4)));
-  c->timed("knn_prefilter", (double)nq * n * B.dp * 2, [&] {
-    pmk::knn_prefilter(c->stream, B.xb.p, B.xn.as<float>(), n, Q.xb.p, Q.xn.as<float>(), nq, B.dp, cand.as<uint32_t>()); });
-  c->timed("knn_rerank", (double)nq * pmk::knn_top() * dim * 4, [&] {
-    pmk::knn_rerank(c->stream, B.x.as<float>(), n, (uint32_t)dim, Q.x.as<float>(), nq, cand.as<uint32_t>(), k, false,
-                    out.as<uint32_t>(), dist.as<float>(), len.as<uint32_t>()); });
-  std::vector<uint32_t> o(nq * k), l(nq);
+  CHK(knn_upload(c, base, n, (uint32_t)dim, B, exact));
+  CHK(knn_upload(c, queries, nq, (uint32_t)dim, Q, exact));
+  KnnOut o;
+  CHK(knn_device(c, B, n, Q, nq, (uint32_t)dim, k, false, true, exact, o, fallback));
+  std::vector<uint32_t> out(nq * k), l(nq);
   std::vector<float> dd(nq * k);
-  HIPCHK(hipMemcpyAsync(o.data(), out.p, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(dd.data(), dist.p, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(l.data(), len.p, nq * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(out.data(), o.out.p, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(dd.data(), o.dist.p, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(l.data(), o.len.p, nq * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (uint64_t i = 0; i < nq; ++i)
     for (uint32_t j = 0; j < k; ++j) {
-      ids[i * k + j] = j < l[i] ? (int64_t)o[i * k + j] : -1;
+      ids[i * k + j] = j < l[i] ? (int64_t)out[i * k + j] : -1;
       if (dists) dists[i * k + j] = j < l[i] ? dd[i * k + j] : INFINITY;
     }
   return 0;
 }
+extern "C" int pm_knn(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                      uint32_t k, int64_t* ids, float* dists) {
+  return knn_impl(c, base, n, dim, queries, nq, k, ids, dists, false, nullptr);
+}
+extern "C" int pm_knn_exact(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries,
+                            uint64_t nq, uint32_t k, int64_t* ids, float* dists, uint64_t* fallback_rows) {
+  if (fallback_rows) *fallback_rows = 0;
+  return knn_impl(c, base, n, dim, queries, nq, k, ids, dists, true, fallback_rows);
+}
 
-extern "C" int pm_build_graph(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
-                              uint64_t seed, uint32_t* graph, double* times) {
+// pm_build_graph and pm_build_graph_exact
+static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
+                            uint64_t seed, uint32_t* graph, double* times, bool exact, uint64_t* fallback) {
   if (!c || !vectors || !graph) return fail(PM_EINVAL, "NULL argument");
   const uint32_t K = (uint32_t)((float)m * 1.5f);   // int(float32(m)*1.5) NGT results (build_graph.go:398)
   if (m == 0 || m > pmk::prune_max_m() || K + 1 > pmk::knn_top())
@@ -89,26 +149,20 @@ extern "C" int pm_build_graph(pm_ctx* c, const float* vectors, uint64_t n, uint6
   hipStream_t st = c->stream;
   auto t0 = Clock::now();
   KnnDev X;
-  CHK(knn_upload(c, vectors, n, (uint32_t)dim, X));
-  DevBuf cand, ck, clen, g1, len1, err;
-  CHK(cand.reserve(n * pmk::knn_top() * 4));
-  CHK(ck.reserve(n * K * 4));
-  CHK(clen.reserve(n * 4));
+  CHK(knn_upload(c, vectors, n, (uint32_t)dim, X, exact));
+  KnnOut kn;
+  DevBuf g1, len1, err;
   CHK(g1.reserve(n * m * 4));
   CHK(len1.reserve(n * 4));
   CHK(err.reserve(4));
   HIPCHK(hipMemsetAsync(err.p, 0, 4, st));
   // candidates: NGT.Search(u, 1.5m) with u removed (:398-410), exact here
-  c->timed("knn_prefilter", (double)n * n * X.dp * 2, [&] {
-    pmk::knn_prefilter(st, X.xb.p, X.xn.as<float>(), n, X.xb.p, X.xn.as<float>(), n, X.dp, cand.as<uint32_t>()); });
-  c->timed("knn_rerank", (double)n * pmk::knn_top() * dim * 4, [&] {
-    pmk::knn_rerank(st, X.x.as<float>(), n, (uint32_t)dim, X.x.as<float>(), n, cand.as<uint32_t>(), K, true,
-                    ck.as<uint32_t>(), nullptr, clen.as<uint32_t>()); });
+  CHK(knn_device(c, X, n, X, n, (uint32_t)dim, K, true, false, exact, kn, fallback));
   HIPCHK(hipStreamSynchronize(st));
   auto t1 = Clock::now();
   // first pass: robustPrune(vectors, u, candidates, m, alpha) (:413-414)
   c->timed("prune", 0.0, [&] {
-    pmk::prune(st, X.x.as<float>(), (uint32_t)dim, nullptr, n, nullptr, K, clen.as<uint32_t>(), ck.as<uint32_t>(),
+    pmk::prune(st, X.x.as<float>(), (uint32_t)dim, nullptr, n, nullptr, K, kn.len.as<uint32_t>(), kn.out.as<uint32_t>(),
                (uint32_t)m, alpha, g1.as<uint32_t>(), len1.as<uint32_t>(), err.as<uint32_t>()); });
   std::vector<uint32_t> G(n * m), L1(n);
   uint32_t e = 0;
@@ -256,4 +310,14 @@ extern "C" int pm_build_graph(pm_ctx* c, const float* vectors, uint64_t n, uint6
     times[3] = std::chrono::duration<double>(t4 - t3).count();   // second robustPrune
   }
   return 0;
+}
+extern "C" int pm_build_graph(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
+                              uint64_t seed, uint32_t* graph, double* times) {
+  return build_graph_impl(c, vectors, n, dim, m, alpha, seed, graph, times, false, nullptr);
+}
+extern "C" int pm_build_graph_exact(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m,
+                                    float alpha, uint64_t seed, uint32_t* graph, double* times,
+                                    uint64_t* fallback_rows) {
+  if (fallback_rows) *fallback_rows = 0;
+  return build_graph_impl(c, vectors, n, dim, m, alpha, seed, graph, times, true, fallback_rows);
 }

@@ -20,6 +20,18 @@
 // result equals a brute-force L2Dist ranking bit for bit.  For general float
 // data the prefilter ranks by bf16-rounded distances and keeps 64 candidates
 // for the exact re-rank of the top K (K <= 48 in the graph build).
+//
+// The exact variants (pm_knn_exact, pm_build_graph_exact) are
+// exact for every finite float input:
+//   k_to_bf16x2        rows -> hi = bf16(x), lo = bf16(x - hi), f32 norms of x,
+//                      the largest norm
+//   k_knn_bf16x3       k_knn_bf16 with q.x = hi.hi' + hi.lo' + lo.hi' (three
+//                      MFMAs per k-step, 64-column tiles); also the prefilter
+//                      distance tau of each row's 64th key
+//   k_knn_rerank_cert  k_knn_rerank plus the certificate: the row is exact if
+//                      its K-th re-ranked distance < tau - eps; other rows go
+//                      to a list
+//   k_knn_brute        the listed rows by brute force in L2Dist order
 #include <hip/hip_runtime.h>
 
 #include "pm_internal.h"
@@ -34,6 +46,7 @@ constexpr int kKnnCols = 128;     // base rows per tile
 constexpr int kKnnTop = 64;       // prefilter keys kept per query row
 constexpr int kKnnThreads = 512;  // 8 waves: 2 row blocks x 4 column blocks of 32x32
 constexpr uint64_t kNoKey = ~0ull;
+constexpr int kKnnMaxDim = 192;   // the widest row knn_pad_dim() accepts
 
 // rows [n][dim] f32 -> out [n][dp] bf16 (zero padded), norms [n] = sum of the
 // squared bf16 values in element order (exact for integer-valued rows)
@@ -58,6 +71,34 @@ __global__ void __launch_bounds__(kBlock) k_to_bf16(const float* __restrict__ ro
   if (lane == 0) norms[r] = s;
 }
 
+// The split form of k_to_bf16: hi = bf16(x), lo = bf16(x - hi) (x - hi is exact
+// in f32), both [n][dp] zero padded; norms [n] = sum of the squared f32 values
+// in the same fixed order.  maxnorm (nullable) is raised to the largest norm:
+// norms are >= +0, so their bit order is their value order and a NaN's bits
+// lie above every number's.
+__global__ void __launch_bounds__(kBlock) k_to_bf16x2(const float* __restrict__ rows, uint64_t n, uint32_t dim,
+                                                      uint32_t dp, __bf16* __restrict__ hi, __bf16* __restrict__ lo,
+                                                      float* __restrict__ norms, uint32_t* __restrict__ maxnorm) {
+  const uint64_t r = (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (r >= n) return;
+  float s = 0.0f;
+  for (uint32_t c0 = 0; c0 < dp; c0 += 64) {
+    const uint32_t c = c0 + lane;
+    const float v = c < dim ? rows[r * dim + c] : 0.0f;
+    const __bf16 b = (__bf16)v;
+    hi[r * dp + c] = b;
+    lo[r * dp + c] = (__bf16)__fsub_rn(v, (float)b);
+    float sq = __fmul_rn(v, v);
+    for (int o = 1; o < 64; o <<= 1) sq = __fadd_rn(sq, __shfl_xor(sq, o));
+    s = __fadd_rn(s, sq);
+  }
+  if (lane == 0) {
+    norms[r] = s;
+    if (maxnorm) atomicMax(maxnorm, __float_as_uint(s));
+  }
+}
+
 template <int DP>
 struct KnnLds {
   uint64_t top[kKnnRows][kKnnTop];          // sorted ascending per row
@@ -72,18 +113,23 @@ __device__ __forceinline__ uint64_t shfl_up64(uint64_t v, int d) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
+  return ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), l) << 32) |
+         __builtin_amdgcn_readlane((uint32_t)v, l);
+}
+
+// Insert the wave-uniform key x into the sorted top-64 t (lane i holds entry i).
+__device__ __forceinline__ uint64_t knn_insert(uint64_t t, uint64_t x, uint32_t lane) {
+  if (x >= readlane64(t, 63)) return t;   // uniform: x and the last key are wave-uniform
+  const uint32_t pos = __popcll(__ballot(t < x));
+  const uint64_t up = shfl_up64(t, 1);
+  return lane < pos ? t : (lane == pos ? x : up);
+}
+
 // Merge the row's insertion buffer into its sorted top-64 (lane i holds entry i).
 __device__ __forceinline__ void knn_merge_row(uint64_t* top, const uint64_t* buf, uint32_t n, uint32_t lane) {
   uint64_t t = top[lane];
-  for (uint32_t e = 0; e < n; ++e) {
-    const uint64_t x = buf[e];
-    const uint64_t last = ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(t >> 32), 63) << 32) |
-                          __builtin_amdgcn_readlane((uint32_t)t, 63);
-    if (x >= last) continue;   // uniform: x and last are wave-uniform
-    const uint32_t pos = __popcll(__ballot(t < x));
-    const uint64_t up = shfl_up64(t, 1);
-    t = lane < pos ? t : (lane == pos ? x : up);
-  }
+  for (uint32_t e = 0; e < n; ++e) t = knn_insert(t, buf[e], lane);
   top[lane] = t;
 }
 
@@ -196,6 +242,171 @@ __global__ void __launch_bounds__(kKnnThreads) k_knn_bf16(const __bf16* __restri
   }
 }
 
+// The split form of k_knn_bf16 (pm_knn_exact): rows are hi + lo (k_to_bf16x2)
+// and q.x is hi.hi' + hi.lo' + lo.hi', three MFMAs per k-step into one
+// accumulator, the two small terms of every k-step before the hi.hi' terms.
+// Both halves of a base tile lie in LDS, so the tile is 64 columns wide and the
+// workgroup has 4 waves (2 row blocks x 2 column blocks of 32x32); each wave
+// keeps both halves of its 32 query rows in registers.  Besides the 64
+// candidate ids a row gets tau, the prefilter distance of its 64th key (NaN
+// while fewer than 64 keys exist): every base row outside the candidates has
+// a prefilter distance >= tau.  The fixed-count loops are unrolled by pragma:
+// left alone, the compiler keeps some of them rolled at DP = 128 and indexes
+// the register arrays through select chains (35,000 instructions).
+constexpr int kKnn3Cols = 64;
+constexpr int kKnn3Threads = 256;
+
+template <int DP>
+struct Knn3Lds {
+  uint64_t top[kKnnRows][kKnnTop];
+  uint64_t buf[kKnnRows][kKnn3Cols];
+  uint32_t cnt[kKnnRows];
+  uint32_t any[2];
+  __bf16 bh[kKnn3Cols][DP + 8];
+  __bf16 bl[kKnn3Cols][DP + 8];
+};
+
+template <int DP>
+__global__ void __launch_bounds__(kKnn3Threads) k_knn_bf16x3(const __bf16* __restrict__ Xh,
+                                                             const __bf16* __restrict__ Xl,
+                                                             const float* __restrict__ xn, uint64_t N,
+                                                             const __bf16* __restrict__ Qh,
+                                                             const __bf16* __restrict__ Ql,
+                                                             const float* __restrict__ qn, uint64_t M,
+                                                             uint32_t* __restrict__ out, float* __restrict__ tau) {
+  constexpr int KS = DP / 16;
+  constexpr int CH = kKnn3Cols * DP / 8;            // 16-B chunks per tile half
+  constexpr int PER = CH / kKnn3Threads;
+  constexpr int MR = kKnnRows / (kKnn3Threads / 64);   // rows each wave merges
+  static_assert(CH % kKnn3Threads == 0, "tile chunks");
+  __shared__ Knn3Lds<DP> L;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint32_t rb = 32 * (w & 1), cb = 32 * (w >> 1);
+  const uint32_t r32 = lane & 31, h = lane >> 5;
+  const uint64_t row0 = (uint64_t)blockIdx.x * kKnnRows;
+
+  for (uint32_t i = tid; i < kKnnRows * kKnnTop; i += kKnn3Threads) (&L.top[0][0])[i] = kNoKey;
+  if (tid < kKnnRows) L.cnt[tid] = 0;
+  if (tid < 2) L.any[tid] = 0;
+
+  bf16x8 ah[KS], al[KS];
+  {
+    const uint64_t qr = row0 + rb + r32;
+    #pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      if (qr < M) {
+        ah[s] = *(const bf16x8*)(Qh + qr * DP + 16 * s + 8 * h);
+        al[s] = *(const bf16x8*)(Ql + qr * DP + 16 * s + 8 * h);
+      } else {
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) ah[s][j] = (__bf16)0.0f;
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) al[s][j] = (__bf16)0.0f;
+      }
+    }
+  }
+  float qnr[16];
+  uint32_t thi[16];
+  #pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const uint64_t qr = row0 + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
+    qnr[i] = qr < M ? qn[qr] : 0.0f;
+    thi[i] = 0xffffffffu;
+  }
+  const uint64_t T = (N + kKnn3Cols - 1) / kKnn3Cols;
+  uint4 preh[PER], prel[PER];
+  auto load_tile = [&](uint64_t t) {
+    const uint64_t c0 = t * kKnn3Cols;
+    #pragma unroll
+    for (int p = 0; p < PER; ++p) {
+      const uint32_t q = tid + p * kKnn3Threads;
+      const uint32_t j = q / (DP / 8), off = (q % (DP / 8)) * 8;
+      if (c0 + j < N) {
+        preh[p] = *(const uint4*)(Xh + (c0 + j) * DP + off);
+        prel[p] = *(const uint4*)(Xl + (c0 + j) * DP + off);
+      } else {
+        preh[p] = make_uint4(0, 0, 0, 0);
+        prel[p] = make_uint4(0, 0, 0, 0);
+      }
+    }
+  };
+  auto store_tile = [&]() {
+    #pragma unroll
+    for (int p = 0; p < PER; ++p) {
+      const uint32_t q = tid + p * kKnn3Threads;
+      const uint32_t j = q / (DP / 8), off = (q % (DP / 8)) * 8;
+      *(uint4*)&L.bh[j][off] = preh[p];
+      *(uint4*)&L.bl[j][off] = prel[p];
+    }
+  };
+  load_tile(0);
+  store_tile();
+  __syncthreads();
+  for (uint64_t t = 0; t < T; ++t) {
+    if (t + 1 < T) load_tile(t + 1);   // in flight during the MFMAs
+    f32x16 acc = {};
+    #pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const bf16x8 bh = *(const bf16x8*)&L.bh[cb + r32][16 * s + 8 * h];
+      const bf16x8 bl = *(const bf16x8*)&L.bl[cb + r32][16 * s + 8 * h];
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[s], bh, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bl, acc, 0, 0, 0);
+    }
+    #pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const bf16x8 bh = *(const bf16x8*)&L.bh[cb + r32][16 * s + 8 * h];
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[s], bh, acc, 0, 0, 0);
+    }
+    const uint64_t col = t * kKnn3Cols + cb + r32;
+    if (col < N) {
+      const float cn = xn[col];
+      #pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const uint32_t lr = rb + (i & 3) + 8 * (i >> 2) + 4 * h;
+        float d = __fsub_rn(__fadd_rn(qnr[i], cn), __fmul_rn(2.0f, acc[i]));
+        d = d < 0.0f ? 0.0f : d;
+        const uint32_t db = __float_as_uint(d);
+        if (db <= thi[i]) {
+          const uint64_t key = ((uint64_t)db << 32) | (uint32_t)col;
+          if (db < thi[i] || key < L.top[lr][kKnnTop - 1]) {
+            const uint32_t slot = atomicAdd(&L.cnt[lr], 1u);
+            L.buf[lr][slot] = key;
+            L.any[t & 1] = 1;
+          }
+        }
+      }
+    }
+    if (tid == 0) L.any[(t + 1) & 1] = 0;
+    __syncthreads();
+    const bool merged = L.any[t & 1] != 0;   // uniform
+    if (merged) {
+      for (uint32_t r = w * MR; r < w * MR + MR; ++r) {
+        const uint32_t n = L.cnt[r];
+        if (n) knn_merge_row(L.top[r], L.buf[r], n, lane);
+      }
+    }
+    if (t + 1 < T) store_tile();
+    __syncthreads();
+    if (merged) {
+      if (lane < MR) L.cnt[w * MR + lane] = 0;
+      #pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const uint32_t lr = rb + (i & 3) + 8 * (i >> 2) + 4 * h;
+        thi[i] = (uint32_t)(L.top[lr][kKnnTop - 1] >> 32);
+      }
+    }
+    // cnt resets must land before the next tile's inserts
+    if (merged) __syncthreads();
+  }
+  for (uint32_t r = w * MR; r < w * MR + MR; ++r) {
+    const uint64_t qr = row0 + r;
+    if (qr < M) {
+      out[qr * kKnnTop + lane] = (uint32_t)L.top[r][lane];
+      if (lane == kKnnTop - 1) tau[qr] = __uint_as_float((uint32_t)(L.top[r][lane] >> 32));
+    }
+  }
+}
+
 // 8-lane L2Dist of a (global f32) and b (global f32) in the reference order;
 // every lane of the group returns the distance.
 __device__ __forceinline__ float l2_group8(const float* __restrict__ a, const float* __restrict__ b, uint32_t dim,
@@ -231,6 +442,42 @@ __device__ __forceinline__ uint64_t wave_sort64(uint64_t x, uint32_t lane) {
   return x;
 }
 
+// One wave's re-rank of a query row: exact L2Dist of the 64 candidates, keys
+// (dist, id) in the wave's LDS row, sorted; lane i returns the i-th key.
+__device__ __forceinline__ uint64_t knn_rerank_keys(const float* __restrict__ X, uint64_t N, uint32_t dim,
+                                                    const float* __restrict__ q, const uint32_t* __restrict__ cand,
+                                                    uint64_t* keys, uint32_t lane) {
+  const uint32_t g = lane >> 3, k = lane & 7;
+  for (uint32_t r = 0; r < 8; ++r) {
+    const uint32_t c = r * 8 + g;
+    const uint32_t id = cand[c];
+    const bool ok = id < N;
+    const float d = l2_group8(X + (ok ? (uint64_t)id : 0) * dim, q, dim, k);
+    if (k == 0) keys[c] = ok ? (((uint64_t)__float_as_uint(d) << 32) | id) : kNoKey;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // this wave's LDS keys visible to its lanes
+  __builtin_amdgcn_wave_barrier();
+  return wave_sort64(keys[lane], lane);
+}
+
+// The first K of a row's sorted keys x (self dropped when self_base: the
+// reference removes u from NGT's K results) go to out[row][K], their count to
+// len[row].
+__device__ __forceinline__ void knn_emit(uint64_t x, uint64_t row, uint32_t K, int self_base, uint32_t lane,
+                                         uint32_t* __restrict__ out, float* __restrict__ dist_out,
+                                         uint32_t* __restrict__ len) {
+  const uint32_t id = (uint32_t)x;
+  const bool in = lane < K && x != kNoKey;
+  const bool self = self_base && id == (uint32_t)row;
+  const uint64_t keep = __ballot(in && !self);
+  const uint32_t pos = __popcll(keep & ((1ull << lane) - 1));
+  if (in && !self) {
+    out[row * K + pos] = id;
+    if (dist_out) dist_out[row * K + pos] = __uint_as_float((uint32_t)(x >> 32));
+  }
+  if (lane == 0) len[row] = __popcll(keep);
+}
+
 // One wave per query row: exact L2Dist of the 64 candidates, keys (dist, id),
 // sorted; the first K (self dropped when self_base) go to out[row][K], their
 // count to len[row].
@@ -243,29 +490,92 @@ __global__ void __launch_bounds__(kBlock) k_knn_rerank(const float* __restrict__
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint64_t row = (uint64_t)blockIdx.x * (kBlock / 64) + w;
   if (row >= M) return;
-  const float* q = Q + row * dim;
-  const uint32_t g = lane >> 3, k = lane & 7;
-  for (uint32_t r = 0; r < 8; ++r) {
-    const uint32_t c = r * 8 + g;
-    const uint32_t id = cand[row * kKnnTop + c];
-    const bool ok = id < N;
-    const float d = l2_group8(X + (ok ? (uint64_t)id : 0) * dim, q, dim, k);
-    if (k == 0) keys[w][c] = ok ? (((uint64_t)__float_as_uint(d) << 32) | id) : kNoKey;
+  const uint64_t x = knn_rerank_keys(X, N, dim, Q + row * dim, cand + row * kKnnTop, keys[w], lane);
+  knn_emit(x, row, K, self_base, lane, out, dist_out, len);
+}
+
+// Bounds of the certificate: eps = crel (qn + maxnorm) +
+// kCertAbs bounds |prefilter distance - L2Dist| of k_knn_bf16x3 for every base
+// row while qn + maxnorm <= kCertMaxSum (no overflow in the products or sums).
+constexpr float kCertAbs = 0x1.0p-50f;
+constexpr float kCertMaxSum = 0x1.0p126f;
+
+// k_knn_rerank with the certificate of pm_knn_exact.  The row's result is the
+// brute-force one if N <= 64 (every base row is a candidate) or if the K-th
+// re-ranked distance is < tau - eps: a base row outside the candidates has a
+// prefilter distance >= tau, so an L2Dist >= tau - eps, strictly above all K
+// kept keys.  A NaN or an infinity anywhere fails the comparison.  Uncertified
+// rows are appended to list (their count in nlist) for k_knn_brute.
+__global__ void __launch_bounds__(kBlock) k_knn_rerank_cert(const float* __restrict__ X, uint64_t N, uint32_t dim,
+                                                            const float* __restrict__ Q, uint64_t M,
+                                                            const uint32_t* __restrict__ cand, uint32_t K,
+                                                            int self_base, uint32_t* __restrict__ out,
+                                                            float* __restrict__ dist_out, uint32_t* __restrict__ len,
+                                                            const float* __restrict__ qn,
+                                                            const float* __restrict__ tau,
+                                                            const uint32_t* __restrict__ maxnorm, float crel,
+                                                            uint64_t* __restrict__ list,
+                                                            unsigned long long* __restrict__ nlist) {
+  __shared__ uint64_t keys[kBlock / 64][64];
+  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint64_t row = (uint64_t)blockIdx.x * (kBlock / 64) + w;
+  if (row >= M) return;
+  const uint64_t x = knn_rerank_keys(X, N, dim, Q + row * dim, cand + row * kKnnTop, keys[w], lane);
+  knn_emit(x, row, K, self_base, lane, out, dist_out, len);
+  if (lane == K - 1 && N > kKnnTop) {
+    const float dk = __uint_as_float((uint32_t)(x >> 32));
+    const float sum = __fadd_rn(qn[row], __uint_as_float(*maxnorm));
+    // rounded up: the factor covers the two roundings of the product and the sum
+    const float eps = __fadd_rn(__fmul_rn(__fmul_rn(sum, crel), 1.0f + 0x1.0p-20f), kCertAbs);
+    const bool ok = x != kNoKey && sum <= kCertMaxSum && (double)dk < (double)tau[row] - (double)eps;
+    if (!ok) list[atomicAdd(nlist, 1ull)] = row;
   }
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // this wave's LDS keys visible to its lanes
-  __builtin_amdgcn_wave_barrier();
-  uint64_t x = wave_sort64(keys[w][lane], lane);
-  // the first K keys; self dropped (the reference removes u from NGT's K results)
-  const uint32_t id = (uint32_t)x;
-  const bool in = lane < K && x != kNoKey;
-  const bool self = self_base && id == (uint32_t)row;
-  const uint64_t keep = __ballot(in && !self);
-  const uint32_t pos = __popcll(keep & ((1ull << lane) - 1));
-  if (in && !self) {
-    out[row * K + pos] = id;
-    if (dist_out) dist_out[row * K + pos] = __uint_as_float((uint32_t)(x >> 32));
+}
+
+// The exact fallback of pm_knn_exact: one workgroup per listed query row
+// streams all N base rows, L2Dist in the reference order by 8-lane groups (the
+// query row in LDS); each wave keeps the sorted 64 smallest (dist, id) keys of
+// its rows in registers with the 64th as threshold, wave 0 merges the four and
+// writes the first K as k_knn_rerank does.
+struct BruteLds {
+  uint64_t top[kBlock / 64][kKnnTop];
+  float q[kKnnMaxDim];
+};
+
+__global__ void __launch_bounds__(kBlock) k_knn_brute(const float* __restrict__ X, uint64_t N, uint32_t dim,
+                                                      const float* __restrict__ Q,
+                                                      const uint64_t* __restrict__ list, uint64_t nlist, uint32_t K,
+                                                      int self_base, uint32_t* __restrict__ out,
+                                                      float* __restrict__ dist_out, uint32_t* __restrict__ len) {
+  __shared__ BruteLds L;
+  constexpr uint32_t W = kBlock / 64;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 3, k = lane & 7;
+  for (uint64_t e = blockIdx.x; e < nlist; e += gridDim.x) {
+    const uint64_t row = list[e];
+    for (uint32_t i = tid; i < dim; i += kBlock) L.q[i] = Q[row * dim + i];
+    __syncthreads();
+    uint64_t t = kNoKey;
+    for (uint64_t r0 = 8 * w; r0 < N; r0 += 8 * W) {   // uniform per wave: every lane stays active
+      const uint64_t r = r0 + g;
+      const bool ok = r < N;
+      const float d = l2_group8(X + (ok ? r : 0) * dim, L.q, dim, k);
+      const uint64_t key = ok ? (((uint64_t)__float_as_uint(d) << 32) | r) : kNoKey;
+      uint64_t m = __ballot(k == 0 && key < readlane64(t, 63));
+      while (m) {
+        const int src = __builtin_ctzll(m);
+        m &= m - 1;
+        t = knn_insert(t, readlane64(key, src), lane);
+      }
+    }
+    L.top[w][lane] = t;
+    __syncthreads();
+    if (w == 0) {
+      for (uint32_t o = 1; o < W; ++o)
+        for (uint32_t i = 0; i < kKnnTop; ++i) t = knn_insert(t, L.top[o][i], lane);
+      knn_emit(t, row, K, self_base, lane, out, dist_out, len);
+    }
+    __syncthreads();   // L.q and L.top are reused by the next listed row
   }
-  if (lane == 0) len[row] = __popcll(keep);
 }
 
 constexpr int kPruneMaxL = 4096;   // candidates per vertex held in LDS
@@ -429,6 +739,45 @@ void knn_rerank(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const 
   if (!M) return;
   hipLaunchKernelGGL(k_knn_rerank, dim3(gcdiv(M, kBlock / 64)), dim3(kBlock), 0, st, X, N, dim, Q, M, cand, K,
                      (int)self_base, out, dist, len);
+}
+void to_bf16x2(hipStream_t st, const float* rows, uint64_t n, uint32_t dim, uint32_t dp, void* hi, void* lo,
+               float* norms, uint32_t* maxnorm) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_to_bf16x2, dim3(gcdiv(n, kBlock / 64)), dim3(kBlock), 0, st, rows, n, dim, dp, (__bf16*)hi,
+                     (__bf16*)lo, norms, maxnorm);
+}
+void knn_prefilter_x3(hipStream_t st, const void* Xh, const void* Xl, const float* xn, uint64_t N, const void* Qh,
+                      const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau) {
+  if (!M) return;
+  const dim3 grid(gcdiv(M, kKnnRows));
+  if (dp == 128)
+    hipLaunchKernelGGL(k_knn_bf16x3<128>, grid, dim3(kKnn3Threads), 0, st, (const __bf16*)Xh, (const __bf16*)Xl, xn,
+                       N, (const __bf16*)Qh, (const __bf16*)Ql, qn, M, out, tau);
+  else
+    hipLaunchKernelGGL(k_knn_bf16x3<192>, grid, dim3(kKnn3Threads), 0, st, (const __bf16*)Xh, (const __bf16*)Xl, xn,
+                       N, (const __bf16*)Qh, (const __bf16*)Ql, qn, M, out, tau);
+}
+// the prefilter's 3 dp products summed with at most 2^-23
+// relative error per add, doubled for whatever order and alignment the matrix
+// core uses; 2^-16 (1 + 2^-6) for the lo residues and the lo.lo' term; 2^-17 for
+// the norm sums, the final qn + xn - 2 acc and L2Dist's own rounding.
+float knn_cert_rel(uint32_t dp) {
+  return (float)(2.0 * (3.0 * dp + 8.0) * 0x1.0p-23 + 0x1.0p-16 * (1.0 + 0x1.0p-6) + 0x1.0p-17);
+}
+void knn_rerank_cert(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
+                     const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len,
+                     const float* qn, const float* tau, const uint32_t* maxnorm, uint32_t dp, uint64_t* list,
+                     uint64_t* nlist) {
+  if (!M) return;
+  hipLaunchKernelGGL(k_knn_rerank_cert, dim3(gcdiv(M, kBlock / 64)), dim3(kBlock), 0, st, X, N, dim, Q, M, cand, K,
+                     (int)self_base, out, dist, len, qn, tau, maxnorm, knn_cert_rel(dp), list,
+                     (unsigned long long*)nlist);
+}
+void knn_brute(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, const uint64_t* list,
+               uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len) {
+  if (!nlist) return;
+  hipLaunchKernelGGL(k_knn_brute, dim3((unsigned)(nlist < (1u << 20) ? nlist : (1u << 20))), dim3(kBlock), 0, st, X, N, dim,
+                     Q, list, nlist, K, (int)self_base, out, dist, len);
 }
 void prune(hipStream_t st, const float* X, uint32_t dim, const uint32_t* verts, uint64_t nverts,
            const uint64_t* offs, uint64_t stride, const uint32_t* lens, const uint32_t* ids, uint32_t m,

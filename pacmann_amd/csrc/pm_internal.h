@@ -444,6 +444,21 @@ void knn_prefilter(hipStream_t st, const void* X, const float* xn, uint64_t N, c
                    uint64_t M, uint32_t dp, uint32_t* out);
 void knn_rerank(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
                 const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
+// the exact variants (pm_knn_exact): split rows hi + lo with f32 norms and the largest norm's bits,
+// the three-product prefilter with each row's 64th prefilter distance tau, the re-rank with the
+// certificate (uncertified rows appended to list, counted in *nlist), the brute-force fallback of
+// the listed rows, and the relative part of the certificate's eps for rows of width dp
+void to_bf16x2(hipStream_t st, const float* rows, uint64_t n, uint32_t dim, uint32_t dp, void* hi, void* lo,
+               float* norms, uint32_t* maxnorm);
+void knn_prefilter_x3(hipStream_t st, const void* Xh, const void* Xl, const float* xn, uint64_t N, const void* Qh,
+                      const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau);
+float knn_cert_rel(uint32_t dp);
+void knn_rerank_cert(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
+                     const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len,
+                     const float* qn, const float* tau, const uint32_t* maxnorm, uint32_t dp, uint64_t* list,
+                     uint64_t* nlist);
+void knn_brute(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, const uint64_t* list,
+               uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
 void prune(hipStream_t st, const float* X, uint32_t dim, const uint32_t* verts, uint64_t nverts,
            const uint64_t* offs, uint64_t stride, const uint32_t* lens, const uint32_t* ids, uint32_t m,
            float alpha, uint32_t* out, uint32_t* out_len, uint32_t* err, const uint32_t* sorted_pos = nullptr,
