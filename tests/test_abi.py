@@ -43,11 +43,10 @@ def test_host_key_schedule_matches_oracle(oracle):
 
 
 def test_last_error_crosses_files():
-    """One argument-checked entry point of every layer of the host side (the
-    csrc/pm_*.cpp files, and the layers pm_engine.cpp still holds together):
-    each fails with PM_EINVAL before any HIP call, and pm_last_error, which
-    lives in pm_ctx.cpp, returns that call's text: the error text is one per
-    thread, not one per file."""
+    """One argument-checked entry point of every host file (csrc/pm_*.cpp, one
+    per layer): each fails with PM_EINVAL before any HIP call, and
+    pm_last_error, which lives in pm_ctx.cpp, returns that call's text: the
+    error text is one per thread, not one per file."""
     import pacmann_amd as pm
     L = pm.lib()
     PM_EINVAL = -1   # include/pacmann.h
@@ -69,6 +68,18 @@ def test_last_error_crosses_files():
         assert L.pm_last_error() == b"ctx is NULL"
         assert call() == PM_EINVAL, layer
         assert L.pm_last_error() == want, layer
+
+
+def test_build_lists_cover_csrc():
+    """Every source and header under csrc/ is in the build lists, so that
+    needs_build() sees a change to any of them and no file is left unlinked."""
+    from pacmann_amd import build
+    csrc = ROOT / "pacmann_amd" / "csrc"
+    sources = sorted(p for p in csrc.iterdir() if p.suffix in (".hip", ".cpp"))
+    headers = sorted(csrc.glob("*.h"))
+    assert sources and headers
+    assert [p for p in sources if p not in build.SOURCES] == []
+    assert [p for p in headers if p not in build.HEADERS] == []
 
 
 def test_no_gpu_raises_loudly():

@@ -48,7 +48,7 @@ def _rank(rank, world, port, out_dir, backend, fault=None):
     import torch
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    if fault and rank == fault[0]:   # this rank's team 0 fails at shared step fault[1] (pm_engine.cpp fault seam)
+    if fault and rank == fault[0]:   # this rank's team 0 fails at shared step fault[1] (pm_group.cpp fault seam)
         os.environ["PM_FAULT_ROUND"] = str(fault[1])
     if backend == "nccl":
         torch.cuda.set_device(0)
@@ -140,7 +140,7 @@ def test_sharded_search_rank_failure_gloo_world2():
     error instead of leaving rank 0 inside a collective: the failed rank takes
     its team's next combine turn with the error word set, every rank reads the
     nonzero sum and stops that team, and the other team stops at its next
-    turn (pm_engine.cpp group_exchange)."""
+    turn (pm_group.cpp group_exchange)."""
     import torch.multiprocessing as mp
     with tempfile.TemporaryDirectory() as d:
         mp.spawn(_rank, args=(2, _free_port(), d, "gloo", (1, 7)), nprocs=2, join=True)

@@ -1,5 +1,5 @@
 """Per-round critical path of the pooled serving loop from its host trace
-(PM_TEAM_TRACE=<file>; pm_engine.cpp TeamTrace).
+(PM_TEAM_TRACE=<file>; pm_group.cpp TeamTrace).
 
 python tools/team_rounds.py TRACE.csv
 

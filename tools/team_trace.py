@@ -1,4 +1,4 @@
-"""Summary of a pooled serving loop's host trace (PM_TEAM_TRACE=<file>, pm_engine.cpp TeamTrace).
+"""Summary of a pooled serving loop's host trace (PM_TEAM_TRACE=<file>, pm_group.cpp TeamTrace).
 
 python tools/team_trace.py TRACE.csv [t0_ms t1_ms]
 
