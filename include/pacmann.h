@@ -80,6 +80,14 @@ int pm_timing_enable(pm_ctx* ctx, int level);
  * 2 (the general form).  -2 restores the environment's choice (PM_MATCH_PART,
  * PM_MATCH_PART8, PM_MATCH_RESOLVE).  "aes_bs": the preprocessing's PRF tables
  * by the bitsliced VALU AES (1) or the T-table AES (0, default; -1: PM_AES_BS).
+ * "fold_rot": the hint fold of ChunkSize 512 / 1,024 partitions by the
+ * bank-rotated kernel over a fold image of the DB (1) or by the pipelined fold
+ * over the rows themselves (0), which is also what runs when the image does
+ * not fit in device memory; -1: PM_FOLD_ROT (default on); any other value is
+ * PM_EINVAL.  Read when a server or client is created, never later: each keeps
+ * the form it was created with for all its preprocessings, a client of a server
+ * without an image goes without one, and clients preprocessed as one group
+ * must agree (PM_EINVAL otherwise).
  * "device_loop": the batched serving loop on the device (1 / 0; -1 automatic).
  * "fault_drl_query" (tests): the device loop fails before queueing query
  * `value` (-1 off); its sessions are then unusable (every later call on them

@@ -146,6 +146,11 @@ extern "C" int pm_set_option(const char* name, int value) {
   if (!strcmp(name, "device_loop")) { g_device_loop.store(value < 0 ? -1 : value); return 0; }
   if (!strcmp(name, "fault_drl_query")) { g_fault_drl_query.store(value); return 0; }
   if (!strcmp(name, "aes_bs")) { pmk::set_aes_bs(value); return 0; }
+  if (!strcmp(name, "fold_rot")) {
+    if (value < -1 || value > 1) return fail(PM_EINVAL, "fold_rot takes 1, 0 or -1");
+    pmk::set_fold_rot(value);
+    return 0;
+  }
   if (pmk::set_option(name, value)) return fail(PM_EINVAL, std::string("unknown option ") + name);
   return 0;
 }

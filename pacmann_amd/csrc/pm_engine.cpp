@@ -135,9 +135,12 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
     HIPCHK(hipStreamSynchronize(ctx->stream));
   }
   // the fold image: a second copy of the owned partitions' rows, laid out for
-  // k_prep_fold_rot (CS 512 and 1,024 shapes; PM_FOLD_ROT=0 disables it).  It is
-  // skipped, and the fold reads the rows themselves (k_prep_fold_pipe), when
-  // it would take more than a quarter of the device memory still free.
+  // k_prep_fold_rot (CS 512 and 1,024 shapes; pm_set_option "fold_rot" 0 or
+  // PM_FOLD_ROT=0 disables it).  It is skipped, and the fold reads the rows
+  // themselves (k_prep_fold_pipe), when it would take more than a quarter of
+  // the device memory still free, or for a client of a server without one.
+  // The option is read here and nowhere later: off_img decides the table
+  // allocation below and the fold form of every preprocessing of this engine.
   uint64_t off_img = 0;
   if (!g->owned_list.empty() && pmk::fold_image_ok(g->minCS, g->maxCS, (uint32_t)g->E)) {
     for (uint32_t i : g->owned_list) {
@@ -357,10 +360,17 @@ int engine_prep_launch(pm_ctx* c, const Engine* g, const PmPart* dp, int np, con
       HIPCHK(hipMemsetAsync(d.rval, 0, (uint64_t)d.SS * d.Qpc * g->E * 8, st));
     }
   } else {
-    int kind = pmk::FOLD_OTHER;
+    // have_img: whether this engine was created with a fold image (its own or its
+    // server's); with the shape it fixes the fold form for the engine's lifetime
+    int kind = pmk::FOLD_GATHER;
     c->timed("prep_fold", fold, [&] { kind = pmk::prep_fold(st, dp, np, g->maxH, g->db->as<uint64_t>(), (uint32_t)g->E, g->minCS,
                                                       g->maxCS, g->zero16.as<uint64_t>(), clients, g->img->p != nullptr, minH); });
-    c->host_add(kind == pmk::FOLD_ROT512 ? HT_FOLD_ROT512 : kind == pmk::FOLD_ROT1024 ? HT_FOLD_ROT1024 : HT_FOLD_OTHER, 0.0);
+    if (kind == pmk::FOLD_ROT512 || kind == pmk::FOLD_ROT1024) {
+      c->host_add(kind == pmk::FOLD_ROT512 ? HT_FOLD_ROT512 : HT_FOLD_ROT1024, 0.0);
+    } else {
+      c->host_add(HT_FOLD_OTHER, 0.0);
+      c->host_add(kind == pmk::FOLD_PIPE ? HT_FOLD_PIPE : kind == pmk::FOLD_BLK ? HT_FOLD_BLK : HT_FOLD_GATHER, 0.0);
+    }
     if (side) HIPCHK(hipStreamWaitEvent(st, c->side_ev[1], 0));
     else c->timed("prep_repl", repl, [&] { pmk::prep_repl(st, dp, np, g->maxRepl, g->db->as<uint64_t>(), (uint32_t)g->E); });
   }

@@ -393,6 +393,12 @@ namespace pmh {
 int prep_clients(pm_ctx* c, DevBuf& pbuf, const std::vector<uint32_t>& lp, const std::vector<Engine*>& who,
                         const std::vector<double*>* mt, HostBuf* stage, hipEvent_t* stage_ev) {
   if (who.empty()) return 0;
+  // one fold form for the set, chosen from who[0]: a client created without the
+  // fold image ("fold_rot" 0) has the chunk-major table the pipelined fold reads,
+  // one created with it does not (checked before any client's state changes)
+  for (Engine* e : who)
+    if ((e->img->p != nullptr) != (who[0]->img->p != nullptr))
+      return fail(PM_EINVAL, "grouped clients were created with and without the fold image");
   auto t0 = Clock::now();
   std::vector<PmPart> hp;
   std::vector<uint64_t> todo;

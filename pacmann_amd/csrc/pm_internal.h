@@ -327,15 +327,29 @@ void prep_offsets(hipStream_t st, const PmPart* dparts, int nparts, uint32_t max
 // VALU (k_prep_offsets_bs, pm_aes_bs.h; profiles/r06/aes: 0.93x), -1 = PM_AES_BS's value
 void set_aes_bs(int v);
 // dparts: `clients` clients of each partition, partition-major (nparts = partitions x clients)
-// returns the fold kernel launched (FOLD_*)
-enum : int { FOLD_OTHER = 0, FOLD_ROT512 = 1, FOLD_ROT1024 = 2 };
+// returns the fold form launched (FOLD_*)
+// The forms of the hint fold: the unblocked gather k_prep_fold<W> (odd E, E < 4,
+// chunks too wide for LDS), the bank-rotated k_prep_fold_rot<512 / 1024> over
+// the fold image, the pipelined k_prep_fold_pipe (one ChunkSize of 512, 1,024
+// or 2,048 and no image) and the double-buffered k_prep_fold_blk<8 / 4 / 2>.
+enum : int { FOLD_GATHER = 0, FOLD_ROT512 = 1, FOLD_ROT1024 = 2, FOLD_PIPE = 3, FOLD_BLK = 4 };
+// The one selection of the form: from the partitions' ChunkSize range, the entry
+// words and whether the engine was created with a fold image.  prep_fold
+// dispatches on it and fold_needs_tab follows from it.
+int fold_form(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img);
+// "fold_rot": 1 / 0 the rotated fold and its image for engines created from now
+// on, -1 = PM_FOLD_ROT's value (default on).  Consulted by fold_image_ok only,
+// i.e. when an engine is created; an existing engine keeps its form.
+void set_fold_rot(int v);
 int prep_fold(hipStream_t st, const PmPart* dparts, int nparts, uint32_t maxH, const uint64_t* db,
               uint32_t E, uint32_t minCS, uint32_t maxCS, const uint64_t* zero16, uint32_t clients = 1,
               bool have_img = false, uint32_t minH = 0);
 void prep_repl(hipStream_t st, const PmPart* dparts, int nparts, uint32_t maxRepl,
                const uint64_t* db, uint32_t E);
-// The bank-rotated fold's DB image (CS 512, even E, E >= 4): whether it applies,
-// its size per partition (words) and the build of one partition's image.
+// The bank-rotated fold's DB image (CS 512 / 1,024, even E, E >= 4): whether an
+// engine being created should have one (the shape fits and "fold_rot" /
+// PM_FOLD_ROT allows it; not to be asked at launch time, see fold_form), its
+// size per partition (words) and the build of one partition's image.
 bool fold_image_ok(uint32_t minCS, uint32_t maxCS, uint32_t E);
 // whether the fold of these shapes reads the chunk-major PRF table PmPart::tab
 // (otherwise it is not allocated: every other reader uses tabT)

@@ -1033,23 +1033,48 @@ void prep_offsets(hipStream_t st, const PmPart* d, int np, uint32_t maxH, uint32
   if (prep_offsets_bitsliced()) prep_offsets_bs(st, d, np, maxH, maxSS);
   else prep_offsets_tt(st, d, np, maxH, maxSS);
 }
+static std::atomic<int> g_fold_rot{-1};
+void set_fold_rot(int v) { g_fold_rot.store(v < 0 ? -1 : (v ? 1 : 0)); }
+// the shapes k_prep_fold_rot folds: one ChunkSize of 512 or 1,024, whole 32-B slices
+static bool fold_rot_shape(uint32_t minCS, uint32_t maxCS, uint32_t E) {
+  return minCS == maxCS && (maxCS == 512 || maxCS == 1024) && E % 2 == 0 && E >= 4;
+}
+// The "fold_rot" option (else PM_FOLD_ROT, default on) is read HERE ONLY, and
+// this is called only while an engine is created: that is where the image is
+// built, shared or skipped and where the chunk-major table is allocated or not
+// (fold_needs_tab).  Every later launch decides from what its engine was
+// created with (have_img) and the shape (fold_form), never from the option: an
+// engine created with the image has no chunk-major table, and the pipelined
+// fold launched on it after the option changed would read PmPart::tab == null.
 bool fold_image_ok(uint32_t minCS, uint32_t maxCS, uint32_t E) {
-  static const bool rot = [] { const char* e = getenv("PM_FOLD_ROT"); return !e || e[0] != '0'; }();
-  return rot && minCS == maxCS && (maxCS == 512 || maxCS == 1024) && E % 2 == 0 && E >= 4;
+  static const bool env = [] { const char* e = getenv("PM_FOLD_ROT"); return !e || e[0] != '0'; }();
+  const int v = g_fold_rot.load();
+  return (v < 0 ? env : v == 1) && fold_rot_shape(minCS, maxCS, E);
+}
+// the double-buffered fold's column-slice width: the widest of 8, 4, 2 words
+// whose two chunk buffers fit in LDS and whose staging fits kFoldMaxItems 16-B
+// items per thread; 0: none does (very wide chunks)
+static uint32_t fold_blk_sw(uint32_t maxCS) {
+  auto fits = [&](uint32_t sw) {
+    return 2ull * (maxCS + 1) * sw * 8 <= 150u * 1024 &&
+           (uint64_t)maxCS * (sw / 2) <= (uint64_t)kFoldMaxItems * kFoldThreads;
+  };
+  uint32_t sw = 8;
+  while (sw > 2 && !fits(sw)) sw /= 2;
+  return fits(sw) ? sw : 0;
+}
+int fold_form(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img) {
+  if ((E & ~3u) == 0) return FOLD_GATHER;   // xorSlices folds nothing: zero parities
+  if (have_img && fold_rot_shape(minCS, maxCS, E)) return maxCS == 512 ? FOLD_ROT512 : FOLD_ROT1024;
+  if (minCS == maxCS && (maxCS == 512 || maxCS == 1024 || maxCS == 2048) && E % 2 == 0) return FOLD_PIPE;
+  if (E % 2 || !fold_blk_sw(maxCS)) return FOLD_GATHER;   // odd entries or very wide chunks
+  return FOLD_BLK;
 }
 bool fold_needs_tab(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img) {
   // the folds that stage a chunk-major PRF table row through LDS (k_prep_fold_pipe
   // / _blk); the rotated fold and the unblocked gather read the tag-major one
-  if ((E & ~3u) == 0) return false;
-  if (have_img && fold_image_ok(minCS, maxCS, E)) return false;
-  const bool pipe = minCS == maxCS && (maxCS == 512 || maxCS == 1024 || maxCS == 2048) && E % 2 == 0;
-  if (pipe) return true;
-  auto fits = [&](uint32_t sw) {   // prep_fold's choice of the double-buffered fold
-    return 2ull * (maxCS + 1) * sw * 8 <= 150u * 1024 && (uint64_t)maxCS * (sw / 2) <= (uint64_t)kFoldMaxItems * kFoldThreads;
-  };
-  uint32_t sw = 8;
-  while (sw > 2 && !fits(sw)) sw /= 2;
-  return fits(sw) && E % 2 == 0;
+  const int form = fold_form(minCS, maxCS, E, have_img);
+  return form == FOLD_PIPE || form == FOLD_BLK;
 }
 uint64_t fold_image_words(uint32_t SS, uint32_t E, uint32_t CS) {
   return (uint64_t)(E / 4) * (SS / rot_nch(CS)) * (kRotBufBytes / 8);
@@ -1064,20 +1089,17 @@ void fold_image(hipStream_t st, uint64_t* img, const uint64_t* rows, uint64_t N,
 int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint64_t* db, uint32_t E,
               uint32_t minCS, uint32_t maxCS, const uint64_t* zero16, uint32_t clients, bool have_img,
                uint32_t minH) {
+  // the form follows from what the engine was created with (have_img) and the
+  // shape alone (fold_form): the same inputs that decided whether PmPart::tab exists
+  const int form = fold_form(minCS, maxCS, E, have_img);
   const uint32_t EX = E & ~3u;
   if (EX == 0) {
     hipLaunchKernelGGL(k_prep_fold<2>, dim3(cdiv((uint64_t)maxH * E, kBlock), np), dim3(kBlock), 0,
                        st, d, db, E);
-    return FOLD_OTHER;
+    return form;
   }
-  // column-slice width: the widest whose double-buffered chunk fits in LDS and
-  // whose staging fits kFoldMaxItems 16-B items per thread
   const uint32_t ng = cdiv(maxH, (uint64_t)kFoldThreads * kFoldHPT);      // pipelined fold
   const uint32_t ngb = cdiv(maxH, (uint64_t)kFoldThreads * kFoldHPTBlk);  // double-buffered fold
-  auto fits = [&](uint32_t sw) {
-    return 2ull * (maxCS + 1) * sw * 8 <= 150u * 1024 &&
-           (uint64_t)maxCS * (sw / 2) <= (uint64_t)kFoldMaxItems * kFoldThreads;
-  };
   auto launch = [&](uint32_t sw, uint32_t w0, uint32_t nsl) {
     const size_t lds = 2ull * (maxCS + 1) * sw * 8;
     const dim3 grid(ngb, nsl, np), blk(kFoldThreads);
@@ -1085,7 +1107,7 @@ int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint
     else if (sw == 4) hipLaunchKernelGGL(k_prep_fold_blk<4>, grid, blk, lds, st, d, db, zero16, E, w0);
     else hipLaunchKernelGGL(k_prep_fold_blk<2>, grid, blk, lds, st, d, db, zero16, E, w0);
   };
-  if (minCS == maxCS && (maxCS == 512 || maxCS == 1024 || maxCS == 2048) && E % 2 == 0) {
+  if (form == FOLD_ROT512 || form == FOLD_ROT1024 || form == FOLD_PIPE) {
     // (SW, G): CS 512 -> (4, 1), 1024 -> (4, 2), 2048 -> (2, 2); EX % SW == 0
     const uint32_t psw = maxCS == 2048 ? 2 : 4, nsl = EX / psw;
     const uint32_t K = clients && np % clients == 0 ? clients : 1, npg = (np / K) * ng;
@@ -1096,19 +1118,18 @@ int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint
 #ifndef PM_FOLD_D512
 #define PM_FOLD_D512 1
 #endif
-    if (have_img && fold_image_ok(minCS, maxCS, E)) {   // the bank-rotated fold (same slices and block order)
+    if (form != FOLD_PIPE) {   // the bank-rotated fold (same slices and block order)
       // virtual hint groups over the K clients of each partition (see the kernel)
       const uint64_t HB = (uint64_t)kFoldThreads * rot_hpl(maxCS);
       const uint32_t ngc = minH >= HB ? 0u : (uint32_t)cdiv(maxH, HB);
       const uint32_t nvg = ngc ? K * ngc : (uint32_t)cdiv((uint64_t)K * maxH, HB), npv = (np / K) * nvg;
       // whole tiles of GB pairs x SB slices, dealt over the 8 XCDs (the kernel's fifth parameter is unused)
       const uint32_t grid = 8 * cdiv((uint64_t)cdiv(npv, PM_ROT_GB) * cdiv(nsl, PM_ROT_SB), 8) * PM_ROT_GB * PM_ROT_SB;
-      if (maxCS == 512) {
+      if (form == FOLD_ROT512)
         hipLaunchKernelGGL(k_prep_fold_rot<512>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, 0u, K, ngc);
-        return FOLD_ROT512;
-      }
-      hipLaunchKernelGGL(k_prep_fold_rot<1024>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, 0u, K, ngc);
-      return FOLD_ROT1024;
+      else
+        hipLaunchKernelGGL(k_prep_fold_rot<1024>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, 0u, K, ngc);
+      return form;
     }
     const uint32_t nb = maxCS == 512 ? PM_FOLD_NB512 : 3;   // LDS buffers: <= 150 KB
     const size_t lds = (size_t)nb * ((maxCS + 1) * psw + kPipeTabWords) * 8;
@@ -1120,23 +1141,22 @@ int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint
       hipLaunchKernelGGL((k_prep_fold_pipe<4, 2, 3>), grid, blk, lds, st, d, db, zero16, E, ng, nsl, npg, K);
     else
       hipLaunchKernelGGL((k_prep_fold_pipe<2, 2, 3>), grid, blk, lds, st, d, db, zero16, E, ng, nsl, npg, K);
-    return FOLD_OTHER;
+    return form;
   }
-  uint32_t sw = 8;
-  while (sw > 2 && !fits(sw)) sw /= 2;
-  if (!fits(sw) || E % 2) {   // very wide chunks or odd entries: the unblocked gather
+  if (form == FOLD_GATHER) {   // very wide chunks or odd entries: the unblocked gather
     if (E % 2 == 0)
       hipLaunchKernelGGL(k_prep_fold<2>, dim3(cdiv((uint64_t)maxH * (EX / 2), kBlock), np),
                          dim3(kBlock), 0, st, d, db, E);
     else
       hipLaunchKernelGGL(k_prep_fold<1>, dim3(cdiv((uint64_t)maxH * EX, kBlock), np), dim3(kBlock), 0,
                          st, d, db, E);
-    return FOLD_OTHER;
+    return form;
   }
+  const uint32_t sw = fold_blk_sw(maxCS);          // FOLD_BLK: sw != 0
   const uint32_t nfull = EX / sw, rem = EX % sw;   // EX is a multiple of 4
   if (nfull) launch(sw, 0, nfull);
   if (rem) launch(rem, nfull * sw, 1);
-  return FOLD_OTHER;
+  return form;
 }
 void prep_repl(hipStream_t st, const PmPart* d, int np, uint32_t maxRepl, const uint64_t* db,
                uint32_t E) {

@@ -143,8 +143,12 @@ def assert_state_equal(a, b):
         assert np.array_equal(a[k], b[k]), k
 
 
-# chunk sizes 512 (pipelined fold, SW 4), 1024 (SW 4, 2 loads per thread),
-# 2048 (SW 2), 256 (double-buffered fold), odd E (unblocked fold), E < 4 (zero)
+# The fold each shape reaches (pmk::fold_form, with the fold image, the default):
+# chunk size 512 (18750 x 4, 62500 x 80) k_prep_fold_rot<512>; 1,024 (262144 x 8)
+# k_prep_fold_rot<1024>; 2,048 (1e6 x 4) the pipelined k_prep_fold_pipe<2,2,3>;
+# 256 (5000 x 6) the double-buffered k_prep_fold_blk<4>; odd E (3000 x 5) and
+# E < 4 (2000 x 2, zero parities) the unblocked k_prep_fold.  The pipelined
+# CS 512 / 1,024 forms and every other form: tests/test_gpu_fold_forms.py.
 @pytest.mark.parametrize("N,E,F", [(18750, 4, 40), (5000, 6, 8), (3000, 5, 8), (2000, 2, 8),
                                    (62500, 80, 8), (262144, 8, 8), (1_000_000, 4, 8)])
 def test_pir_preprocessing_state(ctx, oracle, N, E, F):
