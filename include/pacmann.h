@@ -67,7 +67,19 @@ int         pm_ctx_mem_info(pm_ctx* ctx, uint64_t* free_bytes, uint64_t* total_b
  * bench: a sample, at a fraction of the events' cost).  Host wall-clock
  * accumulators are always on: "host_step_launch", "host_step_wait",
  * "host_step_post", "host_batch_query", "host_gvi_parse", "host_search_knn",
- * "host_knn_init", "host_knn_batch", "host_knn_update", "host_knn_final". */
+ * "host_knn_init", "host_knn_batch", "host_knn_update", "host_knn_final".
+ * So are the step-form counters, one launch count per kernel form as the
+ * launch function itself reported it (total_ms 0 unless noted), on the
+ * context whose stream ran the step: "host_path_match", "host_path_match_part",
+ * "host_path_match_part8" (k_match, k_match_part, k_match_part8);
+ * "host_path_step" (the fused k_step<W>; total_ms = the sum of its gather
+ * helpers per sub-query, a count); "host_path_resolve_lds",
+ * "host_path_resolve_g" (k_resolve<true>, <false>); "host_path_mr_s2",
+ * "host_path_mr_s4", "host_path_mr_general" (k_match_resolve_s<2,256>,
+ * <4,256>, k_match_resolve); "host_path_gather" (k_gather<W>);
+ * "host_path_answer_p5", "host_path_answer_p", "host_path_answer_s",
+ * "host_path_answer_g" (k_answer_p5, k_answer_p, k_answer_s<W,NT>,
+ * k_answer<W>).  DESIGN.md §5 lists the shapes that select each. */
 int pm_timing_enable(pm_ctx* ctx, int level);
 /* "rccl_timeout_s": the bound (seconds) on RCCL communicator creation and
  * its probe (pm_rccl_create / pm_rccl_probe); "verify_records" (sharded loop):

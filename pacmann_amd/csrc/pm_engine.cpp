@@ -731,7 +731,9 @@ int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
     HIPCHK(hipMemsetAsync(B.stamps.p, 0, (uint64_t)grid * 8 * 8, st));
     S.stamps = B.stamps.as<uint64_t>();
 #endif
-    c->timed_ext("step", ans_bytes, [&](pmk::PmEvents ev) { pmk::step_fused(st, S, ev); }, 2);
+    int form = 0;
+    c->timed_ext("step", ans_bytes, [&](pmk::PmEvents ev) { form = pmk::step_fused(st, S, ev); }, 2);
+    c->count_step_form(form, S.nhelp);
     g->step_seq = c->record_done(st);
     HIPCHK(hipGetLastError());
     c->host_add(HT_STEP_LAUNCH, ms_since(t_begin));
@@ -753,7 +755,9 @@ int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
   c->timed_ext("hint_match", (double)nreal * g->maxPH, [&](pmk::PmEvents ev) { path = pmk::step_match(st, S, opts, g->ph8, g->maxPH, max_per_part, ev); }, 2);
   c->count_match_path(path);
   const bool lds = pmk::step_resolve_lds_ok(g->maxPH, max_per_part);
-  c->timed_ext("resolve", 0, [&](pmk::PmEvents ev) { pmk::step_resolve(st, S, lds, ev); }, 2);
+  int form = 0;
+  c->timed_ext("resolve", 0, [&](pmk::PmEvents ev) { form = pmk::step_resolve(st, S, lds, ev); }, 2);
+  c->count_step_form(form);
   if (c->debug_sync) {   // validate every resolution record before k_answer consumes it
     std::vector<PmRes> rr(nsub);
     HIPCHK(hipMemcpy(rr.data(), S.res, nsub * sizeof(PmRes), hipMemcpyDeviceToHost));
@@ -772,9 +776,11 @@ int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
   if (S.nsplit > 1) {
     CHK(B.part_x.reserve((uint64_t)nsub * S.nsplit * (E & ~3ull) * 8));
     S.part_x = B.part_x.as<uint64_t>();
-    c->timed_ext("gather", ans_bytes, [&](pmk::PmEvents ev) { pmk::step_gather(st, S, ev); }, 2);
+    c->timed_ext("gather", ans_bytes, [&](pmk::PmEvents ev) { form = pmk::step_gather(st, S, ev); }, 2);
+    c->count_step_form(form);
   }
-  c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { pmk::step_answer(st, S, g->maxSS, ev); }, 2);
+  c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { form = pmk::step_answer(st, S, g->maxSS, ev); }, 2);
+  c->count_step_form(form);
   g->step_seq = c->record_done(st);
   HIPCHK(hipGetLastError());
   c->host_add(HT_STEP_LAUNCH, ms_since(t_begin));

@@ -128,6 +128,7 @@ int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uint32_t n
   const bool lds = pmk::step_resolve_lds_ok(G.maxPH, max_per_part);
   S.nsplit = c->no_split ? 1 : pmk::step_gather_split(G.maxSS, nsub);
   const pmk::StepOpts opts = pmk::step_opts();   // one snapshot: np_live, the qset and the kernels agree
+  int form = 0;   // what each launcher reports it launched ("host_path_*")
   if (pmk::step_qset_ok(S, opts, lds, G.ph8, G.maxPH, max_per_part, G.maxSS)) {
     S.qw = (G.maxSS + 7) & ~7u;
     CHK(G.qset.reserve((uint64_t)nsub * S.qw * 2));
@@ -146,7 +147,8 @@ int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uint32_t n
       S.stamps = B.stamps.as<uint64_t>();
     }
 #endif
-    c->timed_ext("match_resolve", (double)nreal * G.maxPH, [&](pmk::PmEvents ev) { pmk::step_match_resolve(st, S, opts, G.ph8, G.maxPH, max_per_part, ev); }, 2);
+    c->timed_ext("match_resolve", (double)nreal * G.maxPH, [&](pmk::PmEvents ev) { form = pmk::step_match_resolve(st, S, opts, G.ph8, G.maxPH, max_per_part, ev); }, 2);
+    c->count_step_form(form);
 #ifdef PM_MR_STAMPS
     if (mr_this) {
       CHK(dump_stamps(st, mr_file, &np, sizeof np, B.stamps, np * 8));
@@ -157,12 +159,14 @@ int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uint32_t n
     int path = 0;
     c->timed_ext("hint_match", (double)nreal * G.maxPH, [&](pmk::PmEvents ev) { path = pmk::step_match(st, S, opts, G.ph8, G.maxPH, max_per_part, ev); }, 2);
     c->count_match_path(path);
-    c->timed_ext("resolve", 0, [&](pmk::PmEvents ev) { pmk::step_resolve(st, S, lds, ev); }, 2);
+    c->timed_ext("resolve", 0, [&](pmk::PmEvents ev) { form = pmk::step_resolve(st, S, lds, ev); }, 2);
+    c->count_step_form(form);
   }
   if (S.nsplit > 1) {
     CHK(B.part_x.reserve((uint64_t)nsub * S.nsplit * (G.E & ~3u) * 8));
     S.part_x = B.part_x.as<uint64_t>();
-    c->timed_ext("gather", ans_bytes, [&](pmk::PmEvents ev) { pmk::step_gather(st, S, ev); }, 2);
+    c->timed_ext("gather", ans_bytes, [&](pmk::PmEvents ev) { form = pmk::step_gather(st, S, ev); }, 2);
+    c->count_step_form(form);
   }
 #ifdef PM_ANSWER_STAMPS
   static const char* stamp_file = getenv("PM_ANSWER_STAMPS");   // append {nsub} + nsub x 8 stamps per step
@@ -174,7 +178,8 @@ int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uint32_t n
     S.stamps = B.stamps.as<uint64_t>();
   }
 #endif
-  c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { pmk::step_answer(st, S, G.maxSS, ev); }, 2);
+  c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { form = pmk::step_answer(st, S, G.maxSS, ev); }, 2);
+  c->count_step_form(form);
   if (!G.comb) G.seq = c->record_done(st);   // sharded: group_exchange publishes the records
   HIPCHK(hipGetLastError());
 #ifdef PM_ANSWER_STAMPS

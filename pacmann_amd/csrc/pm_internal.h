@@ -374,26 +374,34 @@ enum : int { MATCH_SUB = 0, MATCH_PART = 1, MATCH_PART8 = 2 };
 int step_match(hipStream_t st, const PmStep& S, const StepOpts& O, bool ph8, uint32_t maxPH,
                uint32_t max_sub_per_part, PmEvents ev = {});
 uint32_t step_match_blocks(uint32_t maxPH);   // k_match workgroups per sub-query
-void step_resolve(hipStream_t st, const PmStep& S, bool lds, PmEvents ev = {});
+// The kernel a step launcher below launched, as its return value: the one
+// record of which instance answered (pm_ctx::count_step_form, "host_path_*").
+// step_fused: k_step<W>; step_resolve: k_resolve<true> / <false>;
+// step_match_resolve: k_match_resolve_s<2,256> / <4,256> / k_match_resolve;
+// step_gather: k_gather<W>; step_answer: k_answer_p5 / k_answer_p /
+// k_answer_s<W,NT> / k_answer<W>.
+enum : int { FORM_STEP = 0, FORM_RESOLVE_LDS, FORM_RESOLVE_G, FORM_MR_S2, FORM_MR_S4, FORM_MR_GENERAL,
+             FORM_GATHER, FORM_ANSWER_P5, FORM_ANSWER_P, FORM_ANSWER_S, FORM_ANSWER_G, FORM_COUNT };
+int step_resolve(hipStream_t st, const PmStep& S, bool lds, PmEvents ev = {});
 // k_match_part + k_resolve fused (batched serving; descriptor already in device memory)
 bool step_match_resolve_ok(const PmStep& S, const StepOpts& O, bool lds);
 bool step_match_resolve_small(const StepOpts& O, bool ph8, uint32_t maxPH, uint32_t max_sub_per_part);
 // ph8: every partition's PH is a multiple of 8
-void step_match_resolve(hipStream_t st, const PmStep& S, const StepOpts& O, bool ph8, uint32_t maxPH,
-                        uint32_t max_sub_per_part, PmEvents ev = {});
+int step_match_resolve(hipStream_t st, const PmStep& S, const StepOpts& O, bool ph8, uint32_t maxPH,
+                       uint32_t max_sub_per_part, PmEvents ev = {});
 // k_step: match, resolve and answer in one launch (descriptor in the kernel
 // arguments, <= 64 sub-queries and <= 8192 hints per partition, <= 256 workgroups)
 bool step_fused_ok(const PmStep& S, uint32_t maxPH, uint32_t max_sub_per_part);
-void step_fused(hipStream_t st, const PmStep& S, PmEvents ev = {});
+int step_fused(hipStream_t st, const PmStep& S, PmEvents ev = {});
 bool step_resolve_lds_ok(uint32_t maxPH, uint32_t max_sub_per_part);
 // k_match_resolve_s writes the query sets for the answer (PmStep::qset); S.nsplit set
 bool step_qset_ok(const PmStep& S, const StepOpts& O, bool lds, bool ph8, uint32_t maxPH,
                   uint32_t max_sub_per_part, uint32_t maxSS);
-void step_answer(hipStream_t st, const PmStep& S, uint32_t maxSS, PmEvents ev = {});
+int step_answer(hipStream_t st, const PmStep& S, uint32_t maxSS, PmEvents ev = {});
 // Split gather ahead of k_answer for wide query sets (SetSize >= 256, BIGANN
 // scale): how many workgroups per sub-query (1: no split), and the launch.
 uint32_t step_gather_split(uint32_t maxSS, uint32_t nsub);
-void step_gather(hipStream_t st, const PmStep& S, PmEvents ev = {});
+int step_gather(hipStream_t st, const PmStep& S, PmEvents ev = {});
 uint32_t step_max_sub_per_part();
 uint32_t step_max_ss();
 uint32_t step_max_e();

@@ -2807,22 +2807,27 @@ bool step_match_resolve_small(const StepOpts& O, bool ph8, uint32_t maxPH, uint3
   const int mode = O.match_resolve;
   return mode == 1 && max_sub_per_part <= kSpecSubs && ph8 && maxPH <= 16u * kResolveBlockG;
 }
-void step_match_resolve(hipStream_t st, const PmStep& S, const StepOpts& O, bool ph8, uint32_t maxPH,
-                        uint32_t max_sub_per_part, PmEvents ev) {
+int step_match_resolve(hipStream_t st, const PmStep& S, const StepOpts& O, bool ph8, uint32_t maxPH,
+                       uint32_t max_sub_per_part, PmEvents ev) {
   // the one-round-trip form where its shapes hold (PM_MATCH_RESOLVE=2: always the general one)
   const bool small = step_match_resolve_small(O, ph8, maxPH, max_sub_per_part);
-  // 256-thread workgroups where they hold the partition's hints: they leave
-  // the GPU's wave slots to the other groups' kernels while wave 0 runs the chain
-  if (small && maxPH <= 8u * 256 * 2)
+  // 256-thread workgroups hold the partition's hints: they leave the GPU's
+  // wave slots to the other groups' kernels while wave 0 runs the chain.
+  // `small` bounds maxPH by 16 * kResolveBlockG = 8,192 = 8 * 256 * 4, so the
+  // two instances cover every small shape: 8 * 256 * 2 = 4,096 hints with two
+  // 8-hint items per thread, 8,192 with four (kResolveBlockG-thread instances
+  // of 8 * 512 = 4,096 and 16 * 512 = 8,192 hints could never be selected)
+  static_assert(16u * kResolveBlockG <= 8u * 256 * 4, "k_match_resolve_s<4, 256> holds every small shape");
+  if (small && maxPH <= 8u * 256 * 2) {
     PM_LAUNCH(ev, (k_match_resolve_s<2, 256>), dim3(S.np), dim3(256), st, S);
-  else if (small && maxPH <= 8u * 256 * 4)
+    return FORM_MR_S2;
+  }
+  if (small) {
     PM_LAUNCH(ev, (k_match_resolve_s<4, 256>), dim3(S.np), dim3(256), st, S);
-  else if (small && maxPH <= 8u * kResolveBlockG)
-    PM_LAUNCH(ev, (k_match_resolve_s<1, kResolveBlockG>), dim3(S.np), dim3(kResolveBlockG), st, S);
-  else if (small && maxPH <= 16u * kResolveBlockG)
-    PM_LAUNCH(ev, (k_match_resolve_s<2, kResolveBlockG>), dim3(S.np), dim3(kResolveBlockG), st, S);
-  else
-    PM_LAUNCH(ev, k_match_resolve<kMatchHints / kBlock>, dim3(S.np), dim3(kResolveBlockG), st, S);
+    return FORM_MR_S4;
+  }
+  PM_LAUNCH(ev, k_match_resolve<kMatchHints / kBlock>, dim3(S.np), dim3(kResolveBlockG), st, S);
+  return FORM_MR_GENERAL;
 }
 bool step_qset_ok(const PmStep& S, const StepOpts& O, bool lds, bool ph8, uint32_t maxPH,
                   uint32_t max_sub_per_part, uint32_t maxSS) {
@@ -2830,9 +2835,10 @@ bool step_qset_ok(const PmStep& S, const StepOpts& O, bool lds, bool ph8, uint32
   return mode == 1 && step_match_resolve_ok(S, O, lds) && max_sub_per_part <= kSpecSubs && ph8 &&
          maxPH <= 16u * kResolveBlockG && maxSS <= kSmallSS && S.nsplit <= 1;
 }
-void step_resolve(hipStream_t st, const PmStep& S, bool lds, PmEvents ev) {
+int step_resolve(hipStream_t st, const PmStep& S, bool lds, PmEvents ev) {
   if (lds) PM_LAUNCH(ev, k_resolve<true>, dim3(S.np), dim3(kBlock), st, S);
   else PM_LAUNCH(ev, k_resolve<false>, dim3(S.np), dim3(kResolveBlockG), st, S);
+  return lds ? FORM_RESOLVE_LDS : FORM_RESOLVE_G;
 }
 bool step_resolve_lds_ok(uint32_t maxPH, uint32_t max_sub_per_part) {
   // the staged (LDS) resolver only for partitions with more sub-queries than
@@ -2842,7 +2848,7 @@ bool step_resolve_lds_ok(uint32_t maxPH, uint32_t max_sub_per_part) {
   return max_sub_per_part > kSpecSubs && maxPH <= kLdsPH &&
          max_sub_per_part * ((maxPH + 63) / 64) <= kLdsBitWords;
 }
-void step_answer(hipStream_t st, const PmStep& S, uint32_t maxSS, PmEvents ev) {
+int step_answer(hipStream_t st, const PmStep& S, uint32_t maxSS, PmEvents ev) {
   // search-sized shapes: the small-LDS instance (PM_ANSWER_NT threads per
   // workgroup, 0 = the generic instance)
   static const int nt = [] { const char* e = getenv("PM_ANSWER_NT"); return e ? atoi(e) : 128; }();
@@ -2861,11 +2867,12 @@ void step_answer(hipStream_t st, const PmStep& S, uint32_t maxSS, PmEvents ev) {
     // 0 = chosen by shape: the 5-wave form for entries of at most 80 words
     // (SIFT1M; MS-MARCO's 100-word entries were not compared and stay at 6)
     const int waves = opt(ov_answer_waves, env_answer_waves);
-    if (waves == 5 || (waves == 0 && S.E <= 80))
+    if (waves == 5 || (waves == 0 && S.E <= 80)) {
       PM_LAUNCH(ev, (k_answer_p5<2, kAnsPNT>), dim3(grid), dim3(kAnsPNT), st, S);
-    else
-      PM_LAUNCH(ev, (k_answer_p<2, kAnsPNT>), dim3(grid), dim3(kAnsPNT), st, S);
-    return;
+      return FORM_ANSWER_P5;
+    }
+    PM_LAUNCH(ev, (k_answer_p<2, kAnsPNT>), dim3(grid), dim3(kAnsPNT), st, S);
+    return FORM_ANSWER_P;
   }
   if (nt && S.nsplit <= 1 && maxSS <= kSmallSS && S.E <= kSmallE) {
     const bool w2 = S.E % 2 == 0;
@@ -2879,10 +2886,11 @@ void step_answer(hipStream_t st, const PmStep& S, uint32_t maxSS, PmEvents ev) {
       if (w2) PM_LAUNCH(ev, (k_answer_s<2, 256>), dim3(S.nsub), dim3(256), st, S);
       else PM_LAUNCH(ev, (k_answer_s<1, 256>), dim3(S.nsub), dim3(256), st, S);
     }
-    return;
+    return FORM_ANSWER_S;
   }
   if (S.E % 2 == 0) PM_LAUNCH(ev, k_answer<2>, dim3(S.nsub), dim3(kAnsBlock), st, S);
   else PM_LAUNCH(ev, k_answer<1>, dim3(S.nsub), dim3(kAnsBlock), st, S);
+  return FORM_ANSWER_G;
 }
 uint32_t step_gather_split(uint32_t maxSS, uint32_t nsub) {
   if (maxSS < 256 || nsub == 0) return 1;
@@ -2895,20 +2903,22 @@ uint32_t step_gather_split(uint32_t maxSS, uint32_t nsub) {
   n = std::max(1u, std::min(n, 64u));
   return n > 1 ? std::max(n, cdiv(maxSS, kGatherMaxRange)) : 1u;   // a range's set fits k_gather's LDS
 }
-void step_gather(hipStream_t st, const PmStep& S, PmEvents ev) {
+int step_gather(hipStream_t st, const PmStep& S, PmEvents ev) {
   const dim3 grid(S.nsplit, S.nsub);
   if (S.E % 2 == 0) PM_LAUNCH(ev, k_gather<2>, grid, dim3(kGatherBlock), st, S);
   else PM_LAUNCH(ev, k_gather<1>, grid, dim3(kGatherBlock), st, S);
+  return FORM_GATHER;
 }
 bool step_fused_ok(const PmStep& S, uint32_t maxPH, uint32_t max_sub_per_part) {
   return S.args_valid && S.recg && S.err_h && max_sub_per_part <= kSpecSubs && maxPH <= kLdsPH &&
          2 * S.nsub + S.np <= 256;
 }
-void step_fused(hipStream_t st, const PmStep& S, PmEvents ev) {
+int step_fused(hipStream_t st, const PmStep& S, PmEvents ev) {
   // S.cblk must be 1 (one match record per sub-query)
   const dim3 grid(2 * S.nsub + S.np + S.nhelp * S.nsub);
   if (S.E % 2 == 0) PM_LAUNCH(ev, k_step<2>, grid, dim3(kStepBlock), st, S);
   else PM_LAUNCH(ev, k_step<1>, grid, dim3(kStepBlock), st, S);
+  return FORM_STEP;
 }
 uint32_t step_max_sub_per_part() { return kMaxSubPerPart; }
 uint32_t step_max_ss() { return kMaxSSLds; }

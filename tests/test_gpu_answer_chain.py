@@ -89,8 +89,11 @@ def test_answer_forms_match_oracle(oracle, ss, nsub, E, waves):
     the responses, the success flags (ok: the DB row; not ok: zero) and every
     partition's refreshed client state equal the oracle's bit for bit.  The
     step counters show that every batch was one shared step of the
-    k_match_resolve_s -> answer chain, with no client served on its own."""
+    k_match_resolve_s -> answer chain, with no client served on its own, and
+    the form counters that it was k_match_resolve_s<2,256> and the asked-for
+    form of the pair kernel."""
     import pacmann_amd as pm
+    from tests.test_gpu_step_forms import assert_forms
     P, S, qn = STEP[nsub]
     assert S * P * qn == nsub
     N, db, ids, seeds = _inputs(ss, nsub, E)
@@ -120,6 +123,7 @@ def test_answer_forms_match_oracle(oracle, ss, nsub, E, waves):
         ctx.timing(False)
         launches = {k: ctx.timing_get(k)[0] for k in ("match_resolve", "answer", "step", "hint_match", "gather")}
         assert launches == {"match_resolve": BATCHES, "answer": BATCHES, "step": 0, "hint_match": 0, "gather": 0}
+        assert_forms(ctx, BATCHES, ("mr_s2", "answer_p5" if waves == 5 else "answer_p"))
         for i, c in enumerate(clients):
             for key in ("FinishedBatchNum", "QueriesMadeInPartition", "PrepCount"):
                 assert c.stats()[key] == stats[i][key], (i, key)
@@ -143,12 +147,15 @@ def test_device_loop_answer_form_and_hand_over(oracle, per_team):
     5-wave form.  The device loop and the host loop on fresh sessions with the
     same seeds give the same answers, graph counts, batch-PIR counters and
     probe responses (dummy counters, FinishedQueryNum, the localCache index) as
-    each other and as the oracle.  Then one host-loop call on the device-loop
+    each other and as the oracle, and the device run's form counters show
+    k_match_part8 -> k_resolve -> k_answer_s for 6 sessions per team and
+    k_match_resolve_s<2,256> -> k_answer_p5 for 8.  Then one host-loop call on the device-loop
     sessions: its steps wait for their own completion records, and its answers
     (which continue the sessions' search streams and PIR state) equal the
     oracle's next query."""
     import pacmann_amd as pm
     from pacmann_amd.synth import random_graph, sift_like_vectors
+    from tests.test_gpu_step_forms import form_counts
     n, S, NQ = 16384, 2 * per_team, 3
     v = sift_like_vectors(n, 128, seed=71)
     graph = random_graph(n, 32, seed=72)
@@ -171,16 +178,26 @@ def test_device_loop_answer_form_and_hand_over(oracle, per_team):
                 x.ctx.timing_reset()
             ans, _, _, mt = pm.search_loop_batched(sess, q_loop, 10, 20, 3, 2, 4)
             dev_steps = sum(x.ctx.timing_get("host_dev_steps")[0] for x in sess)
+            forms = form_counts([x.ctx for x in sess])
             counts = [x.counts() for x in sess]
             stats = [x.PIR.stats() for x in sess]
             extra = [x.PIR.QueryWithMask(probe) for x in sess]
             pm.set_option("device_loop", 0)   # the hand-over: a host-loop call on these sessions
             nxt, _, _, _ = pm.search_loop_batched(sess, q_next, 10, 20, 3, 2, 4)
-            out[mode] = (ans, counts, stats, extra, dev_steps, (mt > 0).all(), nxt)
+            out[mode] = (ans, counts, stats, extra, dev_steps, (mt > 0).all(), nxt, forms)
     finally:
         pm.set_option("device_loop", -1)
-    (a1, c1, s1, x1, st1, m1, n1), (a0, c0, s0, x0, st0, m0, n0) = out[1], out[0]
+    (a1, c1, s1, x1, st1, m1, n1, f1), (a0, c0, s0, x0, st0, m0, n0, _) = out[1], out[0]
     assert st1 == NQ * 20 * 2 and st0 == 0   # every step of the device run on the GPU loop, none of the host run
+    # every device step is one hint-search and one answer launch of the team's form (a session's own steps, if
+    # any, are engine steps: k_step or k_match -> k_resolve -> k_answer_s)
+    if per_team == 8:
+        assert f1["mr_s2"] == f1["answer_p5"] == st1, f1
+        assert f1["match_part8"] == f1["match_part"] == 0, f1
+    else:
+        assert f1["match_part8"] == st1 and f1["resolve_g"] >= st1 and f1["answer_s"] >= st1, f1
+        assert f1["mr_s2"] == f1["answer_p5"] == 0, f1
+    assert f1["mr_s4"] == f1["mr_general"] == f1["answer_p"] == f1["answer_g"] == f1["gather"] == f1["resolve_lds"] == 0, f1
     assert m1 and m0                         # maintenance ran inside both calls
     assert np.array_equal(a1, a0) and np.array_equal(n1, n0)
     assert c1 == c0

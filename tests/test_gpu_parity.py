@@ -603,10 +603,13 @@ def test_search_sessions_batched_wide_entries(ctx, oracle):
     and gather-slice tests but not its RowBufT<kSmallE = 256> row.  Twelve
     sessions in one lock-step group (12 x 48 = 576 sub-queries per shared
     step, above k_answer_p's 512 threshold, with pre-expanded query sets) must
-    take a kernel whose row holds all 258 words and equal independent oracle
-    runs (answers, counts, batch-PIR counters through maintenance)."""
+    take a kernel whose row holds all 258 words (the form counters: every
+    answer launch is the generic k_answer<2>, none a small-row form) and equal
+    independent oracle runs (answers, counts, batch-PIR counters through
+    maintenance)."""
     import pacmann_amd as pm
     from pacmann_amd.synth import random_graph, sift_like_vectors
+    from tests.test_gpu_step_forms import form_counts
     n, dim, m = 4096, 500, 16
     v = sift_like_vectors(n, dim, seed=41)
     graph = random_graph(n, m, seed=42)
@@ -620,7 +623,13 @@ def test_search_sessions_batched_wide_entries(ctx, oracle):
     rng = np.random.default_rng(45)
     qs = np.stack([np.clip(np.rint(v[rng.integers(0, n, 12)] + rng.normal(0, 8, (12, dim))), 0, 255)
                    .astype(np.float32) for _ in seeds])
+    ctxs = [ctx] + [s.ctx for s in sess]
+    for c in ctxs:
+        c.timing_reset()
     ans, wall, on, mt = pm.search_loop_batched(sess, qs, 10, 20, 3, 1, 4)
+    forms = form_counts(ctxs)
+    assert forms["answer_g"] >= 12 * 20, forms   # at least one shared step per round of every query
+    assert forms["answer_s"] == forms["answer_p"] == forms["answer_p5"] == forms["gather"] == 0, forms
     for i, (p, s) in enumerate(seeds):
         o = oracle.Graph(v, graph, pir_seed=p, search_seed=s)
         o.Preprocess()
