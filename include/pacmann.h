@@ -69,7 +69,7 @@ int         pm_ctx_mem_info(pm_ctx* ctx, uint64_t* free_bytes, uint64_t* total_b
  * "host_step_post", "host_batch_query", "host_gvi_parse", "host_search_knn",
  * "host_knn_init", "host_knn_batch", "host_knn_update", "host_knn_final".
  * So are the step-form counters, one launch count per kernel form as the
- * launch function itself reported it (total_ms 0 unless noted), on the
+ * step's plan launched it (total_ms 0 unless noted), on the
  * context whose stream ran the step: "host_path_match", "host_path_match_part",
  * "host_path_match_part8" (k_match, k_match_part, k_match_part8);
  * "host_path_step" (the fused k_step<W>; total_ms = the sum of its gather
@@ -79,7 +79,8 @@ int         pm_ctx_mem_info(pm_ctx* ctx, uint64_t* free_bytes, uint64_t* total_b
  * <4,256>, k_match_resolve); "host_path_gather" (k_gather<W>);
  * "host_path_answer_p5", "host_path_answer_p", "host_path_answer_s",
  * "host_path_answer_g" (k_answer_p5, k_answer_p, k_answer_s<W,NT>,
- * k_answer<W>).  DESIGN.md §5 lists the shapes that select each. */
+ * k_answer<W>).  step_plan (pm_query.hip) is the single place that selects
+ * them (pm_step_plan shows its answer; DESIGN.md §5 lists the shapes). */
 int pm_timing_enable(pm_ctx* ctx, int level);
 /* "rccl_timeout_s": the bound (seconds) on RCCL communicator creation and
  * its probe (pm_rccl_create / pm_rccl_probe); "verify_records" (sharded loop):
@@ -106,6 +107,33 @@ int pm_timing_enable(pm_ctx* ctx, int level);
  * returns PM_EINVAL: their host counters no longer match the device state).
  * PM_EINVAL for an unknown name. */
 int pm_set_option(const char* name, int value);
+/* Which kernels an online step of a given shape launches: the answer of the one
+ * selector every step asks (step_plan, pm_query.hip), under the current
+ * pm_set_option / environment choices.  Host arithmetic only: no context, no
+ * device, nothing launched.  kind: 0 an engine's own step (pm_pir_query,
+ * pm_batchpir_query*), 1 a group's shared step (pm_batchpir_group_query, the
+ * host serving loops), 2 a shared step of the device loop; where the step's
+ * descriptor lives follows from it and the sizes.  np: partitions of the step
+ * (clients x partitions for a shared one), nsub: its sub-queries, np_live:
+ * partitions with at least one, max_per_part: the most sub-queries of one
+ * partition; maxPH / maxSS: the largest PrimaryHintNum / SetSize, E: entry
+ * words, ph8: every PrimaryHintNum is a multiple of 8; no_fuse: PM_NO_FUSE or
+ * PM_DEBUG_SYNC, no_split: PM_NO_SPLIT, no_guess: PM_NO_GUESS of the context.
+ * Out, per launch in the order fused step, match + resolve, hint search,
+ * resolve, gather, answer: the "host_path_*" counter the launch counts in
+ * (pm_timing_enable; NULL: not launched), its grid and block; then the step
+ * fields that go with the forms (nhelp: k_step's gather helpers per sub-query,
+ * nsplit: gather ranges, qw / qset: pre-expanded query sets).  PM_EINVAL for a
+ * NULL argument, an unknown kind or an empty step. */
+typedef struct pm_step_shape {
+  uint32_t kind, np, nsub, np_live, max_per_part, maxPH, maxSS, E, ph8, no_fuse, no_split, no_guess;
+} pm_step_shape;
+typedef struct pm_step_forms {
+  const char* counter[6];
+  uint32_t grid_x[6], grid_y[6], block[6];
+  uint32_t nhelp, nsplit, qw, np_live, cblk, no_guess, qset, args_valid;
+} pm_step_forms;
+int pm_step_plan(const pm_step_shape* shape, pm_step_forms* out);
 int pm_timing_reset(pm_ctx* ctx);
 /* Diagnostics: append one line "kernel,start_us,end_us,ctx" per timed launch
  * of ctx (level >= 2 timing) to the file at `path`, on one time axis for every

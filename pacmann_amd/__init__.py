@@ -59,6 +59,20 @@ class BatchStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class StepShape(C.Structure):   # pm_step_shape
+    _fields_ = [(n, C.c_uint32) for n in
+                "kind np nsub np_live max_per_part maxPH maxSS E ph8 no_fuse no_split no_guess".split()]
+
+
+STEP_STAGES = ("fused", "match_resolve", "match", "resolve", "gather", "answer")   # a plan's launches, in order
+
+
+class StepForms(C.Structure):   # pm_step_forms
+    _fields_ = [("counter", C.c_char_p * 6), ("grid_x", C.c_uint32 * 6), ("grid_y", C.c_uint32 * 6),
+                ("block", C.c_uint32 * 6)] + \
+        [(n, C.c_uint32) for n in "nhelp nsplit qw np_live cblk no_guess qset args_valid".split()]
+
+
 # pm_combine_fn (include/pacmann.h): (user, team, dev_words, nwords, stream) -> 0 on success
 COMBINE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_uint32, vp, u64, vp)
 
@@ -71,6 +85,7 @@ SIGNATURES = {
     "pm_ctx_mem_info": (C.c_int, [vp, u64p, u64p]),
     "pm_timing_enable": (C.c_int, [vp, C.c_int]),
     "pm_set_option": (C.c_int, [C.c_char_p, C.c_int]),
+    "pm_step_plan": (C.c_int, [C.POINTER(StepShape), C.POINTER(StepForms)]),
     "pm_timing_reset": (C.c_int, [vp]),
     "pm_timing_get": (C.c_int, [vp, C.c_char_p, u64p, C.POINTER(dbl), C.POINTER(dbl)]),
     "pm_timing_timeline": (C.c_int, [vp, C.c_char_p]),
@@ -284,6 +299,24 @@ def set_option(name: str, value: int) -> None:
     ("match_part", "match_part8", "match_resolve"; -2 restores the default;
     "aes_bs" and "fold_rot" 1 / 0, -1 restores the default)."""
     _check(lib().pm_set_option(name.encode(), int(value)))
+
+
+def step_plan(kind: int, np_: int, nsub: int, max_per_part: int, maxPH: int, maxSS: int, E: int, *,
+              np_live: int | None = None, ph8: bool = True, no_fuse: bool = False, no_split: bool = False,
+              no_guess: bool = False) -> dict:
+    """pm_step_plan: the kernels a step of this shape launches (no GPU needed).  kind: 0 an engine's own
+    step, 1 a group's shared step, 2 the device loop's.  Returns "forms": the launched kernels' counter names
+    without "host_path_" in launch order, "launches": {stage: (counter, grid_x, grid_y, block)}, and the
+    step fields nhelp, nsplit, qw, np_live, cblk, no_guess, qset, args_valid."""
+    s = StepShape(kind, np_, nsub, np_ if np_live is None else np_live, max_per_part, maxPH, maxSS, E,
+                  int(ph8), int(no_fuse), int(no_split), int(no_guess))
+    f = StepForms()
+    _check(lib().pm_step_plan(C.byref(s), C.byref(f)))
+    out = {n: getattr(f, n) for n, _ in StepForms._fields_[4:]}
+    out["launches"] = {st: (f.counter[i].decode().removeprefix("host_path_"), f.grid_x[i], f.grid_y[i], f.block[i])
+                       for i, st in enumerate(STEP_STAGES) if f.counter[i]}
+    out["forms"] = tuple(v[0] for v in out["launches"].values())
+    return out
 
 
 def l2_batch(query, rows, ctx: Context | None = None) -> np.ndarray:

@@ -154,6 +154,30 @@ extern "C" int pm_set_option(const char* name, int value) {
   if (pmk::set_option(name, value)) return fail(PM_EINVAL, std::string("unknown option ") + name);
   return 0;
 }
+// pmk::step_plan for a shape, as the steps themselves ask it: the caller kind's
+// descriptor facts by StepShape::of_caller (an engine always has k_step's
+// granules), the options' current values.  Host arithmetic only.
+extern "C" int pm_step_plan(const pm_step_shape* in, pm_step_forms* out) {
+  if (!in || !out) return fail(PM_EINVAL, "NULL argument");
+  if (in->kind > (uint32_t)pmk::STEP_DEVICE || in->nsub == 0 || in->np == 0) return fail(PM_EINVAL, "bad step shape");
+  pmk::StepShape s{};
+  s.np = in->np; s.nsub = in->nsub; s.np_live = in->np_live; s.max_per_part = in->max_per_part;
+  s.maxPH = in->maxPH; s.maxSS = in->maxSS; s.E = in->E; s.ph8 = in->ph8 != 0;
+  s.of_caller((int)in->kind, true);
+  s.unfused = in->no_fuse != 0; s.no_split = in->no_split != 0; s.no_guess = in->no_guess != 0;
+  const pmk::StepPlan p = pmk::step_plan(s, pmk::step_opts());
+  static_assert(sizeof out->counter / sizeof out->counter[0] == pmk::STAGE_COUNT, "one slot per launch of a plan");
+  *out = pm_step_forms{};
+  for (int i = 0; i < pmk::STAGE_COUNT; ++i) {
+    const pmk::StepLaunch& l = p.at[i];
+    if (l.form < 0) continue;
+    out->counter[i] = kHostTimerName[pm_ctx::step_counter(i, l.form)];
+    out->grid_x[i] = l.gx; out->grid_y[i] = l.gy; out->block[i] = l.block;
+  }
+  out->nhelp = p.nhelp; out->nsplit = p.nsplit; out->qw = p.qw; out->np_live = p.np_live; out->cblk = p.cblk;
+  out->no_guess = p.no_guess; out->qset = p.qset; out->args_valid = s.args_valid;
+  return 0;
+}
 extern "C" int pm_timing_reset(pm_ctx* c) {
   HIPCHK(hipStreamSynchronize(c->stream));
   for (auto& t : c->launches) { c->pool.push_back(t.a); c->pool.push_back(t.b); }

@@ -249,7 +249,6 @@ static int drl_step(DrlTeam& T, const DrlShape& sh) {
   step_out(S, T.out.p, T.nsub);
   S.E = G.E; S.dim = G.dim; S.nsub = T.nsub; S.np = T.S * G.Pl;
   S.np_live = S.np;
-  S.args_valid = 0;
   S.token = next_token(G.token);
   step_read_window(S, e0->pf_off, e0->pf_len, G.E);
   S.rows_partial = 1;   // the rows stay on the device: no host diagnostic re-reads them
@@ -257,7 +256,7 @@ static int drl_step(DrlTeam& T, const DrlShape& sh) {
   // bytes: every sub-query answered (patched with the round's exact count in timing runs)
   double ans_bytes = 0;
   for (uint32_t li = 0; li < G.Pl; ++li) ans_bytes += answer_bytes(e0->parts[G.lp[li]].d, G.E) * sh.qn * T.S;
-  CHK(group_step_launch(G, S, sh.qn, T.nsub, ans_bytes));
+  CHK(group_step_launch(G, S, pmk::STEP_DEVICE, sh.qn, T.nsub, ans_bytes));
   for (size_t i = before; i < c->launches.size(); ++i)
     if (c->launches[i].name == "answer" || c->launches[i].name == "match_resolve" || c->launches[i].name == "hint_match")
       T.tl.emplace_back(i, T.seq - 1);   // the step the last BEGIN / MID round built (drl_round advanced seq)

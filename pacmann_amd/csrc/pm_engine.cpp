@@ -647,6 +647,104 @@ void post_results(Engine* g, PmOutHdr* hdr, uint64_t* rows, uint32_t nsub, uint3
 #endif
 }
 
+#if defined(PM_STEP_STAMPS) || defined(PM_MR_STAMPS) || defined(PM_ANSWER_STAMPS)
+// Stamp builds: one launch's stamps.  begin: when the environment names a file `f` (and, with
+// `first`, for the run's first 40 such launches only: the file's size), S.stamps
+// = `words` zeroed words; end: `hdr` and the words appended to the file.
+struct LaunchStamps {
+  const char* file = nullptr;
+  uint64_t words = 0;
+  int begin(const char* f, std::atomic<int>* first, hipStream_t st, StepBufs& B, PmStep& S, uint64_t n) {
+    if (!f || (first && first->fetch_add(1) >= 40)) return 0;
+    CHK(B.stamps.reserve(n * 8));
+    HIPCHK(hipMemsetAsync(B.stamps.p, 0, n * 8, st));
+    S.stamps = B.stamps.as<uint64_t>();
+    file = f; words = n;
+    return 0;
+  }
+  int end(hipStream_t st, const StepBufs& B, PmStep& S, const void* hdr, size_t hdr_bytes) {
+    if (!file) return 0;
+    S.stamps = nullptr;
+    return dump_stamps(st, file, hdr, hdr_bytes, B.stamps, words);
+  }
+};
+#endif
+
+// The kernels of one step whose descriptor S is complete, as pmk::step_plan
+// chooses them for `shape`: k_step alone, or the hint search + resolution (one
+// launch, k_match_resolve*, where the shapes hold), the split gather for wide
+// sets and the answer.  Applies the plan's fields to S, reserves what it asks
+// for, times and counts every launch by its form ("host_path_*").
+// after_resolve (if any) runs between the resolution and the gather / answer.
+int step_chain(pm_ctx* c, StepBufs& B, PmStep& S, const pmk::StepShape& shape, uint32_t nreal, double ans_bytes,
+               const std::function<int()>& after_resolve) {
+  hipStream_t st = c->stream;
+  if (shape.desc_shared != (S.subs == S.subs_h && S.sb == S.sb_h))
+    return fail(PM_EINVAL, "step_chain: the descriptor is not where the step's shape says");
+  const pmk::StepPlan plan = pmk::step_plan(shape, pmk::step_opts());
+  S.args_valid = shape.args_valid ? 1u : 0u;
+  S.nsplit = plan.nsplit; S.qw = plan.qw; S.np_live = plan.np_live; S.cblk = plan.cblk; S.nhelp = plan.nhelp; S.no_guess = plan.no_guess;
+  const uint32_t nsub = S.nsub;
+  if (plan.qset) {
+    CHK(B.qset.reserve((uint64_t)nsub * plan.qw * 2));
+    S.qset = B.qset.as<uint16_t>();
+  }
+  if (plan.nsplit > 1) {
+    CHK(B.part_x.reserve((uint64_t)nsub * plan.nsplit * (S.E & ~3u) * 8));
+    S.part_x = B.part_x.as<uint64_t>();
+  }
+  const bool fused = plan.at[pmk::STAGE_FUSED].form >= 0;
+  if (fused) {
+    if (plan.nhelp && !B.helpg.p) {   // the helpers' hand-off granules, on first use (token 0 never marks a step)
+      const size_t nh = (size_t)kArgSubs * kStepHelpMax * kHelpGran * 8;
+      CHK(B.helpg.reserve(nh));
+      HIPCHK(hipMemsetAsync(B.helpg.p, 0, nh, st));
+    }
+    S.helpg = B.helpg.as<uint64_t>();
+  }
+  // Timing level 2: the kernels carry their events in their own dispatch packets.
+  auto run = [&](int stage, const char* name, double bytes) {
+    const int form = plan.at[stage].form;
+    if (form < 0) return;
+    c->timed_ext(name, bytes, [&](pmk::PmEvents ev) { pmk::step_launch(st, S, plan, stage, ev); }, 2);
+    c->host_add(pm_ctx::step_counter(stage, form), stage == pmk::STAGE_FUSED ? plan.nhelp : 0.0);   // k_step: its nhelp
+  };
+#ifdef PM_STEP_STAMPS
+  LaunchStamps ss;   // {grid, nsub, cblk, np} + grid x 8 stamps per k_step (PM_STAMP_FILE)
+  const uint32_t sh[4] = {plan.at[pmk::STAGE_FUSED].gx, nsub, pmk::step_match_blocks(shape.maxPH), S.np};
+  if (fused) CHK(ss.begin(getenv("PM_STAMP_FILE"), nullptr, st, B, S, (uint64_t)sh[0] * 8));
+#endif
+  run(pmk::STAGE_FUSED, "step", ans_bytes);
+#ifdef PM_STEP_STAMPS
+  CHK(ss.end(st, B, S, sh, sizeof sh));
+#endif
+#ifdef PM_MR_STAMPS
+  LaunchStamps ms;   // {np} + np x 8 stamps per k_match_resolve* (PM_MR_STAMPS)
+  static std::atomic<int> mr_steps{0};
+  const uint64_t mh = S.np;
+  if (plan.at[pmk::STAGE_MR].form >= 0) CHK(ms.begin(getenv("PM_MR_STAMPS"), &mr_steps, st, B, S, mh * 8));
+#endif
+  run(pmk::STAGE_MR, "match_resolve", (double)nreal * shape.maxPH);
+#ifdef PM_MR_STAMPS
+  CHK(ms.end(st, B, S, &mh, sizeof mh));
+#endif
+  run(pmk::STAGE_MATCH, "hint_match", (double)nreal * shape.maxPH);
+  run(pmk::STAGE_RESOLVE, "resolve", 0);
+  if (after_resolve) CHK(after_resolve());
+  run(pmk::STAGE_GATHER, "gather", ans_bytes);
+#ifdef PM_ANSWER_STAMPS
+  LaunchStamps as;   // {nsub} + nsub x 8 stamps per answer kernel (PM_ANSWER_STAMPS)
+  static std::atomic<int> ans_steps{0};
+  const uint64_t ah = nsub;
+  if (!fused) CHK(as.begin(getenv("PM_ANSWER_STAMPS"), &ans_steps, st, B, S, ah * 8));
+#endif
+  run(pmk::STAGE_ANSWER, "answer", plan.nsplit > 1 ? 0 : ans_bytes);
+#ifdef PM_ANSWER_STAMPS
+  CHK(as.end(st, B, S, &ah, sizeof ah));
+#endif
+  return 0;
+}
+
 int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
   auto t_begin = Clock::now();
   pm_ctx* c = g->ctx;
@@ -686,79 +784,30 @@ int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
   S.q = q_dev;
   step_out(S, B.out_h.p, nsub);
   S.E = (uint32_t)E; S.dim = q_dev ? dim : 0; S.nsub = nsub; S.np = (uint32_t)g->P;
-  S.args_valid = (nsub <= kArgSubs && g->P <= kArgParts) ? 1u : 0u;
   S.token = next_token(g->step_token);
   step_read_window(S, g->pf_off, g->pf_len, E);
   S.rows_partial = host_rows_partial(c, g->rows_partial);
-  if (S.args_valid) {
-    memcpy(S.subs_a, g->subs.data(), dsub);
-    memcpy(S.sb_a, g->sb.data(), (g->P + 1) * 4);
-  }
   uint32_t nreal = 0;
   for (auto& x : g->subs) nreal += x.kind == SUB_REAL;
-  uint32_t max_per_part = 0;
-  S.np_live = 0;
+  pmk::StepShape shape{};
+  shape.np = (uint32_t)g->P; shape.nsub = nsub; shape.maxPH = g->maxPH; shape.maxSS = g->maxSS; shape.E = (uint32_t)E; shape.ph8 = g->ph8;
   for (uint64_t p = 0; p < g->P; ++p) {
     const uint32_t n = g->sb[p + 1] - g->sb[p];
-    max_per_part = std::max(max_per_part, n);
-    S.np_live += n > 0;
+    shape.max_per_part = std::max(shape.max_per_part, n);
+    shape.np_live += n > 0;
+  }
+  shape.of_caller(pmk::STEP_ENGINE, S.recg && S.err_h);
+  shape.unfused = c->no_fuse || c->debug_sync; shape.no_split = c->no_split; shape.no_guess = c->no_guess;
+  if (shape.args_valid) {
+    memcpy(S.subs_a, g->subs.data(), dsub);
+    memcpy(S.sb_a, g->sb.data(), (g->P + 1) * 4);
   }
   double ans_bytes = 0;
   for (auto& x : g->subs)
     if (x.kind == SUB_REAL || x.kind == SUB_DUMMY) ans_bytes += answer_bytes(g->parts[x.part].d, E);
-  // One launch (k_step) when the step fits it, else the three kernels.
-  // Timing level 2: the kernels carry their events in their own dispatch packets.
-  if (!c->no_fuse && !c->debug_sync && pmk::step_fused_ok(S, g->maxPH, max_per_part)) {
-    S.cblk = 1;   // one match workgroup per sub-query
-    S.no_guess = c->no_guess ? 1u : 0u;
-    // gather helpers where the launch still fits the 240 co-resident
-    // workgroups (one 1,024-thread workgroup per CU): configs[2]'s 32
-    // sub-queries over 16 partitions take PM_STEP_HELP (default 3) each; 0 disables
-    static const int help_env = [] { const char* e = getenv("PM_STEP_HELP"); return e ? atoi(e) : 3; }();
-    S.nhelp = 0;
-    if (help_env > 0 && (E & ~3ull) <= kHelpWords && 2 * nsub + g->P < 240)
-      S.nhelp = std::min<uint32_t>(std::min<uint32_t>(kStepHelpMax, (uint32_t)help_env),
-                                   (uint32_t)((240 - 2 * nsub - g->P) / nsub));
-    if (S.nhelp && !g->helpg.p) {   // the helpers' hand-off granules, on first use (token 0 never marks a step)
-      const size_t nh = (size_t)kArgSubs * kStepHelpMax * kHelpGran * 8;
-      CHK(g->helpg.reserve(nh));
-      HIPCHK(hipMemsetAsync(g->helpg.p, 0, nh, st));
-    }
-    S.helpg = g->helpg.as<uint64_t>();
-#ifdef PM_STEP_STAMPS
-    const uint32_t grid = 2 * nsub + (uint32_t)g->P + S.nhelp * nsub;
-    CHK(B.stamps.reserve((uint64_t)grid * 8 * 8));
-    HIPCHK(hipMemsetAsync(B.stamps.p, 0, (uint64_t)grid * 8 * 8, st));
-    S.stamps = B.stamps.as<uint64_t>();
-#endif
-    int form = 0;
-    c->timed_ext("step", ans_bytes, [&](pmk::PmEvents ev) { form = pmk::step_fused(st, S, ev); }, 2);
-    c->count_step_form(form, S.nhelp);
-    g->step_seq = c->record_done(st);
-    HIPCHK(hipGetLastError());
-    c->host_add(HT_STEP_LAUNCH, ms_since(t_begin));
-    CHK(wait_and_post(g, S, nsub, t_begin));
-    if (*(volatile uint32_t*)S.err_h) {
-      *(volatile uint32_t*)S.err_h = 0;
-      return fail(PM_EHIP, "k_step: a hand-off wait timed out (results of this step are invalid)");
-    }
-#ifdef PM_STEP_STAMPS
-    if (const char* fn = getenv("PM_STAMP_FILE")) {   // append {grid, nsub, cblk, np} + grid x 8 stamps
-      const uint32_t h[4] = {grid, nsub, cblk, (uint32_t)g->P};
-      CHK(dump_stamps(st, fn, h, sizeof h, B.stamps, (uint64_t)grid * 8));
-    }
-#endif
-    return 0;
-  }
-  const pmk::StepOpts opts = pmk::step_opts();
-  int path = 0;
-  c->timed_ext("hint_match", (double)nreal * g->maxPH, [&](pmk::PmEvents ev) { path = pmk::step_match(st, S, opts, g->ph8, g->maxPH, max_per_part, ev); }, 2);
-  c->count_match_path(path);
-  const bool lds = pmk::step_resolve_lds_ok(g->maxPH, max_per_part);
-  int form = 0;
-  c->timed_ext("resolve", 0, [&](pmk::PmEvents ev) { form = pmk::step_resolve(st, S, lds, ev); }, 2);
-  c->count_step_form(form);
-  if (c->debug_sync) {   // validate every resolution record before k_answer consumes it
+  // One launch (k_step) when the step fits it, else the three kernels (pmk::step_plan).
+  std::function<int()> dump_res;
+  if (c->debug_sync) dump_res = [&]() -> int {   // validate every resolution record before k_answer consumes it
     std::vector<PmRes> rr(nsub);
     HIPCHK(hipMemcpy(rr.data(), S.res, nsub * sizeof(PmRes), hipMemcpyDeviceToHost));
     for (uint32_t s = 0; s < nsub; ++s) {
@@ -771,20 +820,18 @@ int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
               s, g->subs[s].part, g->subs[s].kind, (unsigned long)g->subs[s].idx, r.status, r.hit, r.chunk, r.ing,
               r.tag, r.pp, r.slot, r.flags, bad ? "  <-- BAD" : "");
     }
-  }
-  S.nsplit = c->no_split ? 1 : pmk::step_gather_split(g->maxSS, nsub);
-  if (S.nsplit > 1) {
-    CHK(B.part_x.reserve((uint64_t)nsub * S.nsplit * (E & ~3ull) * 8));
-    S.part_x = B.part_x.as<uint64_t>();
-    c->timed_ext("gather", ans_bytes, [&](pmk::PmEvents ev) { form = pmk::step_gather(st, S, ev); }, 2);
-    c->count_step_form(form);
-  }
-  c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { form = pmk::step_answer(st, S, g->maxSS, ev); }, 2);
-  c->count_step_form(form);
+    return 0;
+  };
+  CHK(step_chain(c, B, S, shape, nreal, ans_bytes, dump_res));
   g->step_seq = c->record_done(st);
   HIPCHK(hipGetLastError());
   c->host_add(HT_STEP_LAUNCH, ms_since(t_begin));
-  return wait_and_post(g, S, nsub, t_begin);
+  CHK(wait_and_post(g, S, nsub, t_begin));
+  if (S.err_h && *(volatile uint32_t*)S.err_h) {   // only k_step sets it
+    *(volatile uint32_t*)S.err_h = 0;
+    return fail(PM_EHIP, "k_step: a hand-off wait timed out (results of this step are invalid)");
+  }
+  return 0;
 }
 }  // namespace pmh
 

@@ -12,6 +12,7 @@ struct DbGen;
 struct Engine;
 struct pm_graph;
 struct StepGroup;
+struct StepBufs;
 struct ShardComb;
 
 // ---------------------------------------------------------------------------
@@ -35,6 +36,8 @@ int wait_step(pm_ctx* c, const PmOutHdr* hdr, uint32_t nsub, uint32_t token, con
               size_t row_bytes, size_t pf_off, size_t pf_len, uint64_t seq, pm_ctx* sc = nullptr);
 void post_results(Engine* g, PmOutHdr* hdr, uint64_t* rows, uint32_t nsub, uint32_t base,
                   uint32_t token);
+int step_chain(pm_ctx* c, StepBufs& B, PmStep& S, const pmk::StepShape& shape, uint32_t nreal, double ans_bytes,
+               const std::function<int()>& after_resolve = {});
 int engine_step(Engine* g, const float* q_dev, uint32_t dim);
 void print_stamps(const Engine& e);
 void record_stats(Engine* g, double t);
@@ -58,7 +61,7 @@ void knn_batch(pm_graph* g, int parallel, int benchmarking);
 void knn_update(pm_graph* g, int step);
 void knn_end(pm_graph* g, int k, int64_t* ids_out, int64_t* steps_out);
 // pm_group.cpp
-int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uint32_t nreal, double ans_bytes);
+int group_step_launch(StepGroup& G, PmStep& S, int kind, uint32_t max_per_part, uint32_t nreal, double ans_bytes);
 int prep_clients(pm_ctx* c, DevBuf& pbuf, const std::vector<uint32_t>& lp, const std::vector<Engine*>& who,
                  const std::vector<double*>* mt, HostBuf* stage = nullptr, hipEvent_t* stage_ev = nullptr);
 int team_init(StepGroup& G, pm_graph** gs, uint32_t S);
@@ -127,11 +130,13 @@ struct FlatMap {
 // One step's scratch (k_match -> k_resolve -> [k_gather] -> k_answer), held by
 // an Engine for its own steps and by a StepGroup for its shared ones.  The
 // device buffers are sized by reserve() for nsub sub-queries over np
-// partitions; part_x (split gather), stamps (stamp builds) and the pinned
+// partitions; part_x (split gather), qset, helpg, stamps (stamp builds) and the pinned
 // descriptor / result buffers are reserved where a step needs them.
 // ---------------------------------------------------------------------------
 struct StepBufs {
   DevBuf subs_d, sb_d, bits, cand, meta, spec, res_d, ans, part_x, stamps;
+  DevBuf qset;    // query sets expanded by k_match_resolve_s (PmStep::qset)
+  DevBuf helpg;   // k_step's gather helpers' hand-off granules
   HostBuf desc_h, out_h;
   int reserve(uint32_t nsub, uint32_t np, uint32_t words, uint32_t cblk, uint64_t E) {
     CHK(subs_d.reserve(nsub * sizeof(PmSub)));
@@ -221,7 +226,6 @@ struct Engine {
   std::vector<uint32_t> owned_list;   // owned partitions in order (owned_d holds their PmPart)
   DevBuf qoffs, ans_srv;
   StepBufs buf;   // the step's scratch (engine_step)
-  DevBuf helpg;   // k_step's gather helpers' hand-off granules
   std::vector<double> stamp_sum;   // PM_STAMPS builds: accumulated phase deltas
   uint64_t stamp_n = 0;
   uint32_t step_token = 0;         // PmStep::token of the last step
@@ -370,7 +374,7 @@ struct StepGroup {
   // (drl_team_init) and its kernels keep the pointers: no group_step, nor any
   // other reserve of it, on a DrlTeam's group after that
   StepBufs buf;
-  DevBuf parts_d, done, prep_parts, desc_d, qset;
+  DevBuf parts_d, done, prep_parts, desc_d;
   uint32_t token = 0, pf_w0 = 0, pf_w1 = 0;
   uint64_t seq = 0;   // the last shared step's completion sequence number (pm_ctx::record_done)
   std::vector<PmSub> subs;

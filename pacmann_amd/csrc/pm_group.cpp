@@ -115,79 +115,20 @@ static void group_stage_session(StepGroup& G, uint32_t s) {
 }
 
 namespace pmh {
-// The kernels of one shared step whose descriptor S is complete: the hint
-// search + resolution (k_match_resolve_s where the shapes hold), the split
-// gather for wide sets, the answer; the completion event unless the records
-// go to a combine.  (group_step; the device loop's steps, run_batched_dev.)
-int group_step_launch(StepGroup& G, PmStep& S, uint32_t max_per_part, uint32_t nreal, double ans_bytes) {
+// The kernels of one shared step whose descriptor S is complete (step_chain);
+// the completion event unless the records go to a combine.  kind: STEP_SHARED
+// (group_step) or STEP_DEVICE (the device loop's steps, run_batched_dev).
+int group_step_launch(StepGroup& G, PmStep& S, int kind, uint32_t max_per_part, uint32_t nreal, double ans_bytes) {
   pm_ctx* c = G.c;
-  hipStream_t st = c->stream;
-  const uint32_t nsub = S.nsub;
-  StepBufs& B = G.buf;
   auto t0 = Clock::now();
-  const bool lds = pmk::step_resolve_lds_ok(G.maxPH, max_per_part);
-  S.nsplit = c->no_split ? 1 : pmk::step_gather_split(G.maxSS, nsub);
-  const pmk::StepOpts opts = pmk::step_opts();   // one snapshot: np_live, the qset and the kernels agree
-  int form = 0;   // what each launcher reports it launched ("host_path_*")
-  if (pmk::step_qset_ok(S, opts, lds, G.ph8, G.maxPH, max_per_part, G.maxSS)) {
-    S.qw = (G.maxSS + 7) & ~7u;
-    CHK(G.qset.reserve((uint64_t)nsub * S.qw * 2));
-    S.qset = G.qset.as<uint16_t>();
-  }
-  if (pmk::step_match_resolve_ok(S, opts, lds)) {   // one launch: match + resolve per partition
-    if (pmk::step_match_resolve_small(opts, G.ph8, G.maxPH, max_per_part)) S.np_live = 0;   // resolvers do not count in
-#ifdef PM_MR_STAMPS
-    static const char* mr_file = getenv("PM_MR_STAMPS");   // append {np} + np x 8 stamps per step
-    static std::atomic<int> mr_steps{0};   // the first 40 steps of the run
-    const bool mr_this = mr_file && mr_steps.fetch_add(1) < 40;
-    const uint64_t np = S.np;
-    if (mr_this) {
-      CHK(B.stamps.reserve(np * 8 * 8));
-      HIPCHK(hipMemsetAsync(B.stamps.p, 0, np * 8 * 8, st));
-      S.stamps = B.stamps.as<uint64_t>();
-    }
-#endif
-    c->timed_ext("match_resolve", (double)nreal * G.maxPH, [&](pmk::PmEvents ev) { form = pmk::step_match_resolve(st, S, opts, G.ph8, G.maxPH, max_per_part, ev); }, 2);
-    c->count_step_form(form);
-#ifdef PM_MR_STAMPS
-    if (mr_this) {
-      CHK(dump_stamps(st, mr_file, &np, sizeof np, B.stamps, np * 8));
-      S.stamps = nullptr;
-    }
-#endif
-  } else {
-    int path = 0;
-    c->timed_ext("hint_match", (double)nreal * G.maxPH, [&](pmk::PmEvents ev) { path = pmk::step_match(st, S, opts, G.ph8, G.maxPH, max_per_part, ev); }, 2);
-    c->count_match_path(path);
-    c->timed_ext("resolve", 0, [&](pmk::PmEvents ev) { form = pmk::step_resolve(st, S, lds, ev); }, 2);
-    c->count_step_form(form);
-  }
-  if (S.nsplit > 1) {
-    CHK(B.part_x.reserve((uint64_t)nsub * S.nsplit * (G.E & ~3u) * 8));
-    S.part_x = B.part_x.as<uint64_t>();
-    c->timed_ext("gather", ans_bytes, [&](pmk::PmEvents ev) { form = pmk::step_gather(st, S, ev); }, 2);
-    c->count_step_form(form);
-  }
-#ifdef PM_ANSWER_STAMPS
-  static const char* stamp_file = getenv("PM_ANSWER_STAMPS");   // append {nsub} + nsub x 8 stamps per step
-  static std::atomic<int> stamp_steps{0};   // the first 40 steps of the run (file size)
-  const bool stamp_this = stamp_file && stamp_steps.fetch_add(1) < 40;
-  if (stamp_this) {
-    CHK(B.stamps.reserve((uint64_t)nsub * 8 * 8));
-    HIPCHK(hipMemsetAsync(B.stamps.p, 0, (uint64_t)nsub * 8 * 8, st));
-    S.stamps = B.stamps.as<uint64_t>();
-  }
-#endif
-  c->timed_ext("answer", S.nsplit > 1 ? 0 : ans_bytes, [&](pmk::PmEvents ev) { form = pmk::step_answer(st, S, G.maxSS, ev); }, 2);
-  c->count_step_form(form);
-  if (!G.comb) G.seq = c->record_done(st);   // sharded: group_exchange publishes the records
+  pmk::StepShape shape{};
+  shape.np = S.np; shape.nsub = S.nsub; shape.np_live = S.np_live; shape.max_per_part = max_per_part;
+  shape.maxPH = G.maxPH; shape.maxSS = G.maxSS; shape.E = G.E; shape.ph8 = G.ph8;
+  shape.of_caller(kind, false);
+  shape.unfused = c->no_fuse || c->debug_sync; shape.no_split = c->no_split; shape.no_guess = c->no_guess;
+  CHK(step_chain(c, G.buf, S, shape, nreal, ans_bytes));
+  if (!G.comb) G.seq = c->record_done(c->stream);   // sharded: group_exchange publishes the records
   HIPCHK(hipGetLastError());
-#ifdef PM_ANSWER_STAMPS
-  if (stamp_this) {
-    const uint64_t h = nsub;
-    CHK(dump_stamps(st, stamp_file, &h, sizeof h, B.stamps, (uint64_t)nsub * 8));
-  }
-#endif
   c->host_add(HT_STEP_LAUNCH, ms_since(t0));
   G.pf_w0 = S.pf_w0; G.pf_w1 = S.pf_w1;
   return 0;
@@ -222,7 +163,7 @@ static int group_step(StepGroup& G, const std::vector<char>& in) {
     if (!ss.ok || ss.step != G.nstep) staged = false;
     nsub += ss.n;
   }
-  if (staged && nsub <= kArgSubs && np <= kArgParts) staged = false;   // kernel-argument descriptors: the general way
+  if (staged && pmk::step_args_fit(nsub, np)) staged = false;   // kernel-argument descriptors: the general way
   G.nstep++;
   PmSub* const stage = G.stage_h.as<PmSub>();
   if (staged) {   // compact the slots in place; the partition offsets follow the subs
@@ -292,7 +233,7 @@ static int group_step(StepGroup& G, const std::vector<char>& in) {
   S.subs_h = (const PmSub*)dh;
   S.sb_h = (const uint32_t*)(dh + dsub);
   B.fill(S, words, cblk);
-  if (!(nsub <= kArgSubs && np <= kArgParts)) {
+  if (!pmk::step_args_fit(nsub, np)) {
     // a large descriptor crosses PCIe once, by DMA, instead of as thousands of
     // zero-copy reads by the match workgroups; k_match* stage it from here
     CHK(G.desc_d.reserve(dsub + (np + 1) * 4));
@@ -315,15 +256,14 @@ static int group_step(StepGroup& G, const std::vector<char>& in) {
   }
   S.E = G.E; S.dim = G.dim; S.nsub = nsub; S.np = np;
   S.np_live = np_live;
-  S.args_valid = (nsub <= kArgSubs && np <= kArgParts) ? 1u : 0u;
-  if (S.args_valid) {   // (never the staged form)
+  if (pmk::step_args_fit(nsub, np)) {   // (never the staged form)
     memcpy(S.subs_a, G.subs.data(), dsub);
     memcpy(S.sb_a, G.sb.data(), (np + 1) * 4);
   }
   S.token = next_token(G.token);
   step_read_window(S, e0->pf_off, e0->pf_len, G.E);
   S.rows_partial = host_rows_partial(c, G.rows_partial);
-  return group_step_launch(G, S, max_per_part, nreal, ans_bytes);
+  return group_step_launch(G, S, pmk::STEP_SHARED, max_per_part, nreal, ans_bytes);
 }
 
 // The lines session s's collect will read (its result headers and the row

@@ -101,7 +101,7 @@ struct HostBuf {
 // Host wall-clock accumulators, read back as "host_*" through pm_timing_get.
 // The "host_path_match*" entries count the hint-search kernel each step launched
 // (k_match / k_match_part / k_match_part8; total_ms 0); the other "host_path_*"
-// the step's remaining kernels by the form their launcher returned (pmk::FORM_*;
+// the step's remaining kernels by the form the step's plan launched (pmk::step_plan, pmk::FORM_*;
 // total_ms 0 unless noted): "step" the fused k_step<W>, total_ms = the sum of
 // its gather helpers per sub-query (nhelp; a count, not a time); "resolve_lds"
 // / "resolve_g" k_resolve<true> / <false>; "mr_s2" / "mr_s4" / "mr_general"
@@ -193,11 +193,11 @@ struct pm_ctx {
   uint64_t host_n[HT_COUNT] = {};
   double host_ms[HT_COUNT] = {};
   void host_add(HostTimer t, double ms) { host_n[t]++; host_ms[t] += ms; }
-  void count_match_path(int path) {
-    host_add(path == pmk::MATCH_PART8 ? HT_PATH_MATCH_PART8 : path == pmk::MATCH_PART ? HT_PATH_MATCH_PART : HT_PATH_MATCH, 0.0);
+  // the counter of a step launch: the plan's form at `stage` (pmk::MATCH_* at STAGE_MATCH, else pmk::FORM_*)
+  static HostTimer step_counter(int stage, int form) {
+    if (stage != pmk::STAGE_MATCH) return (HostTimer)(HT_PATH_STEP + form);
+    return form == pmk::MATCH_PART8 ? HT_PATH_MATCH_PART8 : form == pmk::MATCH_PART ? HT_PATH_MATCH_PART : HT_PATH_MATCH;
   }
-  // form: what a step launcher returned (pmk::FORM_*); v: k_step's nhelp
-  void count_step_form(int form, double v = 0.0) { host_add((HostTimer)(HT_PATH_STEP + form), v); }
   std::vector<TimedLaunch> launches;
   std::vector<hipEvent_t> pool;
   hipEvent_t ev() {

@@ -364,44 +364,58 @@ struct PmEvents { hipEvent_t a = nullptr, b = nullptr; };
 // choice (PM_MATCH_PART, PM_MATCH_PART8, PM_MATCH_RESOLVE).  Returns -1 for an
 // unknown name.
 int set_option(const char* name, int value);
-// The selectors' values for one step (read once per step and passed to every
-// selector below, so one step never mixes two settings).
-struct StepOpts { int match_part, match_part8, match_resolve; };
+// The selectors' values for one step: pm_set_option's overrides over the environment's choices, each
+// read once per process (PM_MATCH_PART -1, PM_MATCH_PART8 1, PM_MATCH_RESOLVE 1, PM_ANSWER_WAVES 0,
+// PM_ANSWER_NT 128, PM_ANSWER_PAIR 1, PM_GATHER_SPLIT 0, PM_STEP_HELP 3).  One snapshot per step, so
+// a pm_set_option on another thread cannot split a step between two paths.
+struct StepOpts { int match_part, match_part8, match_resolve, answer_waves, answer_nt, answer_pair, gather_split, step_help; };
 StepOpts step_opts();
-// ph8: every partition's PH is a multiple of 8 (k_match_part8).  Returns the
-// hint-search kernel launched.
-enum : int { MATCH_SUB = 0, MATCH_PART = 1, MATCH_PART8 = 2 };
-int step_match(hipStream_t st, const PmStep& S, const StepOpts& O, bool ph8, uint32_t maxPH,
-               uint32_t max_sub_per_part, PmEvents ev = {});
 uint32_t step_match_blocks(uint32_t maxPH);   // k_match workgroups per sub-query
-// The kernel a step launcher below launched, as its return value: the one
-// record of which instance answered (pm_ctx::count_step_form, "host_path_*").
-// step_fused: k_step<W>; step_resolve: k_resolve<true> / <false>;
-// step_match_resolve: k_match_resolve_s<2,256> / <4,256> / k_match_resolve;
-// step_gather: k_gather<W>; step_answer: k_answer_p5 / k_answer_p /
-// k_answer_s<W,NT> / k_answer<W>.
+// Who builds the step: an engine's own step (engine_step: the device copies of
+// the descriptor differ from the host-visible one), a group's shared step
+// (group_step: a descriptor too large for the kernel arguments is DMA'd and is
+// then its own device copy) or the device loop's (built on the device).
+enum : int { STEP_ENGINE = 0, STEP_SHARED = 1, STEP_DEVICE = 2 };
+// Small steps ship the descriptor inside the kernel arguments (PmStep::args_valid).
+inline bool step_args_fit(uint32_t nsub, uint32_t np) { return nsub <= kArgSubs && np <= kArgParts; }
+// What the choice of a step's kernels depends on, and nothing else.
+struct StepShape {
+  uint32_t np, nsub, np_live, max_per_part, maxPH, maxSS, E;
+  bool ph8;           // every partition's PH is a multiple of 8 (k_match_part8, k_match_resolve_s)
+  // descriptor facts (of_caller)
+  bool args_valid;    // the descriptor travels in the kernel arguments (PmStep::subs_a / sb_a)
+  bool desc_shared;   // PmStep::subs == subs_h and sb == sb_h: the kernels' descriptor is in device memory
+  bool granules;      // k_step's hand-off granules and error word exist
+  // context switches
+  bool unfused;       // PM_NO_FUSE or PM_DEBUG_SYNC
+  bool no_split, no_guess;
+  void of_caller(int kind, bool have_granules) {
+    args_valid = kind != STEP_DEVICE && step_args_fit(nsub, np);
+    desc_shared = kind == STEP_DEVICE || (kind == STEP_SHARED && !args_valid);
+    granules = kind == STEP_ENGINE && have_granules;
+  }
+};
+// The kernels of a step: the hint search (MATCH_*, counted in "host_path_match*")
+// and the forms of the others (FORM_*: the one record of which instance
+// answered, pm_ctx::step_counter, "host_path_*"): k_step<W>; k_resolve<true>
+// / <false>; k_match_resolve_s<2,256> / <4,256> / k_match_resolve; k_gather<W>;
+// k_answer_p5 / k_answer_p / k_answer_s<W,NT> / k_answer<W>.
+enum : int { MATCH_SUB = 0, MATCH_PART = 1, MATCH_PART8 = 2 };
 enum : int { FORM_STEP = 0, FORM_RESOLVE_LDS, FORM_RESOLVE_G, FORM_MR_S2, FORM_MR_S4, FORM_MR_GENERAL,
              FORM_GATHER, FORM_ANSWER_P5, FORM_ANSWER_P, FORM_ANSWER_S, FORM_ANSWER_G, FORM_COUNT };
-int step_resolve(hipStream_t st, const PmStep& S, bool lds, PmEvents ev = {});
-// k_match_part + k_resolve fused (batched serving; descriptor already in device memory)
-bool step_match_resolve_ok(const PmStep& S, const StepOpts& O, bool lds);
-bool step_match_resolve_small(const StepOpts& O, bool ph8, uint32_t maxPH, uint32_t max_sub_per_part);
-// ph8: every partition's PH is a multiple of 8
-int step_match_resolve(hipStream_t st, const PmStep& S, const StepOpts& O, bool ph8, uint32_t maxPH,
-                       uint32_t max_sub_per_part, PmEvents ev = {});
-// k_step: match, resolve and answer in one launch (descriptor in the kernel
-// arguments, <= 64 sub-queries and <= 8192 hints per partition, <= 256 workgroups)
-bool step_fused_ok(const PmStep& S, uint32_t maxPH, uint32_t max_sub_per_part);
-int step_fused(hipStream_t st, const PmStep& S, PmEvents ev = {});
-bool step_resolve_lds_ok(uint32_t maxPH, uint32_t max_sub_per_part);
-// k_match_resolve_s writes the query sets for the answer (PmStep::qset); S.nsplit set
-bool step_qset_ok(const PmStep& S, const StepOpts& O, bool lds, bool ph8, uint32_t maxPH,
-                  uint32_t max_sub_per_part, uint32_t maxSS);
-int step_answer(hipStream_t st, const PmStep& S, uint32_t maxSS, PmEvents ev = {});
-// Split gather ahead of k_answer for wide query sets (SetSize >= 256, BIGANN
-// scale): how many workgroups per sub-query (1: no split), and the launch.
-uint32_t step_gather_split(uint32_t maxSS, uint32_t nsub);
-int step_gather(hipStream_t st, const PmStep& S, PmEvents ev = {});
+// A step's launches in order: FUSED alone, or MR or MATCH + RESOLVE, then GATHER (split sets), then ANSWER.
+enum : int { STAGE_FUSED = 0, STAGE_MR, STAGE_MATCH, STAGE_RESOLVE, STAGE_GATHER, STAGE_ANSWER, STAGE_COUNT };
+struct StepLaunch { int form = -1; uint32_t gx = 0, gy = 1, block = 0; };   // form < 0: not launched; MATCH_* at STAGE_MATCH
+struct StepPlan {
+  StepLaunch at[STAGE_COUNT];
+  // the PmStep fields that must agree with the forms
+  uint32_t nhelp, nsplit, qw, np_live, cblk, no_guess;
+  bool qset;   // k_match_resolve_s expands the query sets (PmStep::qset, [nsub][qw]) and the answer reads them
+};
+// The one selection of a step's kernels, grids and fields: pure (no HIP call, environment or state).
+StepPlan step_plan(const StepShape& s, const StepOpts& O);
+// Issues one launch of a plan (S as the plan says: pmh::step_chain).
+void step_launch(hipStream_t st, const PmStep& S, const StepPlan& plan, int stage, PmEvents ev = {});
 uint32_t step_max_sub_per_part();
 uint32_t step_max_ss();
 uint32_t step_max_e();

@@ -2740,19 +2740,19 @@ static inline unsigned cdiv(uint64_t a, uint64_t b) { return (unsigned)((a + b -
 constexpr int kOptUnset = INT32_MIN;
 static int env_int(const char* name, int def) { const char* e = getenv(name); return e ? atoi(e) : def; }
 static const int env_match_part = env_int("PM_MATCH_PART", -1), env_match_part8 = env_int("PM_MATCH_PART8", 1),
-                 env_match_resolve = env_int("PM_MATCH_RESOLVE", 1), env_answer_waves = env_int("PM_ANSWER_WAVES", 0);
+                 env_match_resolve = env_int("PM_MATCH_RESOLVE", 1), env_answer_waves = env_int("PM_ANSWER_WAVES", 0),
+                 env_answer_nt = env_int("PM_ANSWER_NT", 128), env_answer_pair = env_int("PM_ANSWER_PAIR", 1),
+                 env_gather_split = env_int("PM_GATHER_SPLIT", 0), env_step_help = env_int("PM_STEP_HELP", 3);
 static std::atomic<int> ov_match_part{kOptUnset}, ov_match_part8{kOptUnset}, ov_match_resolve{kOptUnset},
     ov_answer_waves{kOptUnset};
 static int opt(const std::atomic<int>& ov, int env) {
   const int v = ov.load(std::memory_order_relaxed);
   return v != kOptUnset ? v : env;
 }
-// One snapshot per step: every selector of the step reads the same values, so
-// a pm_set_option on another thread cannot split a step between two paths
-// (e.g. np_live = 0 with the general k_match_resolve).
 StepOpts step_opts() {
   return StepOpts{opt(ov_match_part, env_match_part), opt(ov_match_part8, env_match_part8),
-                  opt(ov_match_resolve, env_match_resolve)};
+                  opt(ov_match_resolve, env_match_resolve), opt(ov_answer_waves, env_answer_waves),
+                  env_answer_nt, env_answer_pair, env_gather_split, env_step_help};
 }
 int set_option(const char* name, int value) {
   std::atomic<int>* o = !strcmp(name, "match_part") ? &ov_match_part
@@ -2764,161 +2764,156 @@ int set_option(const char* name, int value) {
   return 0;
 }
 uint32_t step_match_blocks(uint32_t maxPH) { return cdiv(maxPH, kMatchHints); }
-// With events, the launch carries them in its own dispatch packet
-// (hipExtLaunchKernelGGL): the kernel's execution time as the profiler sees it.
-#define PM_LAUNCH(ev, kern, grid, blk, st, ...)                                              \
-  do {                                                                                       \
-    if ((ev).a) hipExtLaunchKernelGGL(kern, grid, blk, 0, st, (ev).a, (ev).b, 0, __VA_ARGS__); \
-    else hipLaunchKernelGGL(kern, grid, blk, 0, st, __VA_ARGS__);                             \
-  } while (0)
-int step_match(hipStream_t st, const PmStep& S, const StepOpts& O, bool ph8, uint32_t maxPH,
-               uint32_t max_sub_per_part, PmEvents ev) {
-  // many partitions with several sub-queries each (batched serving): one
-  // workgroup per (partition, hint block); otherwise one per (sub-query, block)
-  const int mode = O.match_part;
-  const bool part = mode == 1 || (mode == -1 && S.np >= 128 && S.nsub >= 4 * S.np);
-  // PM_MATCH_PART8=0: the LDS-merged form for every PH
-  const int v8 = O.match_part8;
-  // k_match_part8 from 64 partitions with 2+ sub-queries each (BIGANN teams of
-  // 4-6 sessions: k_match's workgroup per (sub-query, block) took 85 us there)
-  const bool part8 = ph8 && v8 && max_sub_per_part <= kPart8Subs && (part || (mode == -1 && S.np >= 64 && S.nsub >= 2 * S.np));
-  if (part8) {
-    PM_LAUNCH(ev, k_match_part8<PM_MATCHPART8_NW>, dim3(cdiv(step_match_blocks(maxPH), PM_MATCHPART8_NW), S.np),
-              dim3(64 * PM_MATCHPART8_NW), st, S);
-    return MATCH_PART8;
+
+// k_step's launch: at most kStepMaxWg workgroups (2 nsub + np without gather
+// helpers), and helpers only while the whole launch stays within the
+// kStepResidentWg co-resident workgroups (one 1,024-thread workgroup per CU)
+constexpr uint32_t kStepMaxWg = 256, kStepResidentWg = 240;
+static_assert(kStepResidentWg <= kStepMaxWg, "a k_step launch with helpers is still a launch step_plan admits");
+
+StepPlan step_plan(const StepShape& s, const StepOpts& O) {
+  StepPlan p{};
+  const uint32_t words = (s.maxPH + 63) / 64, mpp = s.max_per_part;
+  p.np_live = s.np_live;
+  // One launch (k_step) when the step fits it: descriptor in the kernel
+  // arguments, <= 64 sub-queries and <= 8,192 hints per partition
+  if (!s.unfused && s.args_valid && s.granules && mpp <= kSpecSubs && s.maxPH <= kLdsPH &&
+      2 * s.nsub + s.np <= kStepMaxWg) {
+    p.cblk = 1;   // one match workgroup (one match record) per sub-query
+    p.no_guess = s.no_guess ? 1u : 0u;
+    // gather helpers for entries of <= kHelpWords gathered words: configs[2]'s
+    // 32 sub-queries over 16 partitions take PM_STEP_HELP (default 3) each; 0 disables
+    if (O.step_help > 0 && (s.E & ~3u) <= kHelpWords && 2 * s.nsub + s.np < kStepResidentWg)
+      p.nhelp = std::min(std::min(kStepHelpMax, (uint32_t)O.step_help), (kStepResidentWg - 2 * s.nsub - s.np) / s.nsub);
+    p.at[STAGE_FUSED] = {FORM_STEP, 2 * s.nsub + s.np + p.nhelp * s.nsub, 1, kStepBlock};
+    return p;
   }
-  if (part) {
-    PM_LAUNCH(ev, k_match_part<kMatchHints / kBlock>, dim3(step_match_blocks(maxPH), S.np), dim3(kBlock), st, S);
-    return MATCH_PART;
-  }
-  PM_LAUNCH(ev, k_match, dim3(step_match_blocks(maxPH), S.nsub), dim3(kBlock), st, S);
-  return MATCH_SUB;
-}
-bool step_match_resolve_ok(const PmStep& S, const StepOpts& O, bool lds) {
-  const int mode = O.match_resolve;
-  // one workgroup per partition matches every hint of it: search-sized hint
-  // counts only (PH <= 16,384; BIGANN's 57,344 / 114,688 hints per partition
-  // go to k_match_part's workgroup per (partition, hint block) instead)
-  return mode && !lds && !S.args_valid && S.subs == S.subs_h && S.sb == S.sb_h && S.np >= 128 &&
-         S.nsub >= 4 * S.np && S.words <= 256;
-}
-// k_match_resolve_s serves the step (its resolvers do not count in: PmStep::np_live = 0)
-bool step_match_resolve_small(const StepOpts& O, bool ph8, uint32_t maxPH, uint32_t max_sub_per_part) {
-  const int mode = O.match_resolve;
-  return mode == 1 && max_sub_per_part <= kSpecSubs && ph8 && maxPH <= 16u * kResolveBlockG;
-}
-int step_match_resolve(hipStream_t st, const PmStep& S, const StepOpts& O, bool ph8, uint32_t maxPH,
-                       uint32_t max_sub_per_part, PmEvents ev) {
-  // the one-round-trip form where its shapes hold (PM_MATCH_RESOLVE=2: always the general one)
-  const bool small = step_match_resolve_small(O, ph8, maxPH, max_sub_per_part);
-  // 256-thread workgroups hold the partition's hints: they leave the GPU's
-  // wave slots to the other groups' kernels while wave 0 runs the chain.
-  // `small` bounds maxPH by 16 * kResolveBlockG = 8,192 = 8 * 256 * 4, so the
-  // two instances cover every small shape: 8 * 256 * 2 = 4,096 hints with two
-  // 8-hint items per thread, 8,192 with four (kResolveBlockG-thread instances
-  // of 8 * 512 = 4,096 and 16 * 512 = 8,192 hints could never be selected)
-  static_assert(16u * kResolveBlockG <= 8u * 256 * 4, "k_match_resolve_s<4, 256> holds every small shape");
-  if (small && maxPH <= 8u * 256 * 2) {
-    PM_LAUNCH(ev, (k_match_resolve_s<2, 256>), dim3(S.np), dim3(256), st, S);
-    return FORM_MR_S2;
-  }
-  if (small) {
-    PM_LAUNCH(ev, (k_match_resolve_s<4, 256>), dim3(S.np), dim3(256), st, S);
-    return FORM_MR_S4;
-  }
-  PM_LAUNCH(ev, k_match_resolve<kMatchHints / kBlock>, dim3(S.np), dim3(kResolveBlockG), st, S);
-  return FORM_MR_GENERAL;
-}
-bool step_qset_ok(const PmStep& S, const StepOpts& O, bool lds, bool ph8, uint32_t maxPH,
-                  uint32_t max_sub_per_part, uint32_t maxSS) {
-  const int mode = O.match_resolve;
-  return mode == 1 && step_match_resolve_ok(S, O, lds) && max_sub_per_part <= kSpecSubs && ph8 &&
-         maxPH <= 16u * kResolveBlockG && maxSS <= kSmallSS && S.nsplit <= 1;
-}
-int step_resolve(hipStream_t st, const PmStep& S, bool lds, PmEvents ev) {
-  if (lds) PM_LAUNCH(ev, k_resolve<true>, dim3(S.np), dim3(kBlock), st, S);
-  else PM_LAUNCH(ev, k_resolve<false>, dim3(S.np), dim3(kResolveBlockG), st, S);
-  return lds ? FORM_RESOLVE_LDS : FORM_RESOLVE_G;
-}
-bool step_resolve_lds_ok(uint32_t maxPH, uint32_t max_sub_per_part) {
+  p.cblk = step_match_blocks(s.maxPH);
   // the staged (LDS) resolver only for partitions with more sub-queries than
   // the fast prologue takes; otherwise the global-memory form, whose fast
   // prologue is the same and whose 36 KB of LDS (not 117) let four
   // workgroups share a CU
-  return max_sub_per_part > kSpecSubs && maxPH <= kLdsPH &&
-         max_sub_per_part * ((maxPH + 63) / 64) <= kLdsBitWords;
-}
-int step_answer(hipStream_t st, const PmStep& S, uint32_t maxSS, PmEvents ev) {
-  // search-sized shapes: the small-LDS instance (PM_ANSWER_NT threads per
-  // workgroup, 0 = the generic instance)
-  static const int nt = [] { const char* e = getenv("PM_ANSWER_NT"); return e ? atoi(e) : 128; }();
-  // the pipelined pair form (k_answer_p) where its shapes hold: pre-expanded
-  // query sets, one gather segment per thread slice (E & ~3 <= 2 * 128 words)
-  static const int pair = [] { const char* e = getenv("PM_ANSWER_PAIR"); return e ? atoi(e) : 1; }();
-  // the pair form's decoded row lives in RowBufT<kSmallE>: E itself (not only
-  // its gather part E & ~3) must fit, or the epilogue's tail words overrun it
+  const bool lds = mpp > kSpecSubs && s.maxPH <= kLdsPH && mpp * words <= kLdsBitWords;
+  // Split gather ahead of k_answer for wide query sets (SetSize >= 256, BIGANN
+  // scale), workgroups per sub-query (1: no split): >= 48 rows per workgroup,
+  // about 4,096 workgroups in all (two rounds of the GPU's 2,048 resident
+  // 256-thread workgroups; BIGANN-100M's 960 sub-queries: 5 ranges, 96-104 us,
+  // vs 3 ranges at ~2,048 workgroups, 124-143 us), at most 64 per sub-query;
+  // PM_GATHER_SPLIT=n forces n
+  p.nsplit = 1;
+  if (!s.no_split && s.maxSS >= 256 && s.nsub) {
+    uint32_t n = O.gather_split > 0 ? (uint32_t)O.gather_split : std::min(cdiv(s.maxSS, 48), cdiv(4096, s.nsub));
+    n = std::max(1u, std::min(n, 64u));
+    if (n > 1) p.nsplit = std::max(n, cdiv(s.maxSS, kGatherMaxRange));   // a range's set fits k_gather's LDS
+  }
+  // k_match_part + k_resolve in one launch (batched serving; the descriptor in
+  // device memory): one workgroup per partition matches every hint of it, so
+  // search-sized hint counts only (PH <= 16,384; BIGANN's 57,344 / 114,688
+  // hints per partition go to k_match_part's workgroup per (partition, hint
+  // block) instead)
+  const bool mr = O.match_resolve && !lds && !s.args_valid && s.desc_shared && s.np >= 128 && s.nsub >= 4 * s.np &&
+                  words <= 256;
+  if (mr) {
+    // the one-round-trip form k_match_resolve_s where its shapes hold
+    // (PM_MATCH_RESOLVE=2: always the general one); its resolvers do not count
+    // in: np_live = 0
+    const bool small = O.match_resolve == 1 && mpp <= kSpecSubs && s.ph8 && s.maxPH <= 16u * kResolveBlockG;
+    // 256-thread workgroups hold the partition's hints: they leave the GPU's
+    // wave slots to the other groups' kernels while wave 0 runs the chain.
+    // `small` bounds maxPH by 16 * kResolveBlockG = 8,192 = 8 * 256 * 4, so the
+    // two instances cover every small shape: 8 * 256 * 2 = 4,096 hints with two
+    // 8-hint items per thread, 8,192 with four (kResolveBlockG-thread instances
+    // of 8 * 512 = 4,096 and 16 * 512 = 8,192 hints could never be selected)
+    static_assert(16u * kResolveBlockG <= 8u * 256 * 4, "k_match_resolve_s<4, 256> holds every small shape");
+    if (small) {
+      p.np_live = 0;
+      p.at[STAGE_MR] = {s.maxPH <= 8u * 256 * 2 ? FORM_MR_S2 : FORM_MR_S4, s.np, 1, 256};
+      // ... and it writes the query sets for the answer (qw = SetSize rounded up to 8)
+      p.qset = s.maxSS <= kSmallSS && p.nsplit <= 1;
+      if (p.qset) p.qw = (s.maxSS + 7) & ~7u;
+    } else {
+      p.at[STAGE_MR] = {FORM_MR_GENERAL, s.np, 1, kResolveBlockG};
+    }
+  } else {
+    // many partitions with several sub-queries each (batched serving): one
+    // workgroup per (partition, hint block); otherwise one per (sub-query, block)
+    const int mode = O.match_part;
+    const bool part = mode == 1 || (mode == -1 && s.np >= 128 && s.nsub >= 4 * s.np);
+    // k_match_part8 (PM_MATCH_PART8=0: the LDS-merged form for every PH) from 64
+    // partitions with 2+ sub-queries each (BIGANN teams of 4-6 sessions:
+    // k_match's workgroup per (sub-query, block) took 85 us there)
+    const bool part8 = s.ph8 && O.match_part8 && mpp <= kPart8Subs &&
+                       (part || (mode == -1 && s.np >= 64 && s.nsub >= 2 * s.np));
+    if (part8) p.at[STAGE_MATCH] = {MATCH_PART8, cdiv(p.cblk, PM_MATCHPART8_NW), s.np, 64 * PM_MATCHPART8_NW};
+    else if (part) p.at[STAGE_MATCH] = {MATCH_PART, p.cblk, s.np, kBlock};
+    else p.at[STAGE_MATCH] = {MATCH_SUB, p.cblk, s.nsub, kBlock};
+    if (lds) p.at[STAGE_RESOLVE] = {FORM_RESOLVE_LDS, s.np, 1, kBlock};
+    else p.at[STAGE_RESOLVE] = {FORM_RESOLVE_G, s.np, 1, kResolveBlockG};
+  }
+  if (p.nsplit > 1) p.at[STAGE_GATHER] = {FORM_GATHER, p.nsplit, s.nsub, kGatherBlock};
+  // The answer.  The pipelined pair form (k_answer_p, PM_ANSWER_PAIR) where its
+  // shapes hold: pre-expanded query sets, one gather segment per thread slice
+  // (E & ~3 <= 2 * 128 words).  Its decoded row lives in RowBufT<kSmallE>: E
+  // itself (not only its gather part E & ~3) must fit, or the epilogue's tail
+  // words overrun it
   static_assert(2u * kAnsPNT >= kSmallE, "k_answer_p's gather slices must cover a kSmallE row");
-  if (pair && S.qset && S.nsplit <= 1 && maxSS <= kSmallSS && S.E % 2 == 0 && S.E <= kSmallE &&
-      (S.E & ~3u) <= 2u * kAnsPNT && S.nsub >= 2 * 256) {
-    // PM_ANSWER_PK_MAX sub-queries per workgroup (2: every workgroup of a
-    // 6,144-sub-query step resident at once)
-    const uint32_t grid = (S.nsub + PM_ANSWER_PK_MAX - 1) / PM_ANSWER_PK_MAX;
+  const bool search_sized = p.nsplit <= 1 && s.maxSS <= kSmallSS && s.E <= kSmallE;
+  if (O.answer_pair && p.qset && search_sized && s.E % 2 == 0 && (s.E & ~3u) <= 2u * kAnsPNT && s.nsub >= 2 * 256) {
     // PM_ANSWER_WAVES / "answer_waves": 6 = the 80-VGPR form, 5 = k_answer_p5,
     // 0 = chosen by shape: the 5-wave form for entries of at most 80 words
-    // (SIFT1M; MS-MARCO's 100-word entries were not compared and stay at 6)
-    const int waves = opt(ov_answer_waves, env_answer_waves);
-    if (waves == 5 || (waves == 0 && S.E <= 80)) {
-      PM_LAUNCH(ev, (k_answer_p5<2, kAnsPNT>), dim3(grid), dim3(kAnsPNT), st, S);
-      return FORM_ANSWER_P5;
-    }
-    PM_LAUNCH(ev, (k_answer_p<2, kAnsPNT>), dim3(grid), dim3(kAnsPNT), st, S);
-    return FORM_ANSWER_P;
+    // (SIFT1M; MS-MARCO's 100-word entries were not compared and stay at 6).
+    // PM_ANSWER_PK_MAX sub-queries per workgroup (2: every workgroup of a
+    // 6,144-sub-query step resident at once)
+    const bool p5 = O.answer_waves == 5 || (O.answer_waves == 0 && s.E <= 80);
+    p.at[STAGE_ANSWER] = {p5 ? FORM_ANSWER_P5 : FORM_ANSWER_P, cdiv(s.nsub, PM_ANSWER_PK_MAX), 1, kAnsPNT};
+  } else if (O.answer_nt && search_sized) {
+    // search-sized shapes: the small-LDS instance (PM_ANSWER_NT threads per
+    // workgroup: 128, 512, else 256; 0 = the generic instance)
+    p.at[STAGE_ANSWER] = {FORM_ANSWER_S, s.nsub, 1, O.answer_nt == 128 ? 128u : O.answer_nt == 512 ? 512u : 256u};
+  } else {
+    p.at[STAGE_ANSWER] = {FORM_ANSWER_G, s.nsub, 1, kAnsBlock};
   }
-  if (nt && S.nsplit <= 1 && maxSS <= kSmallSS && S.E <= kSmallE) {
-    const bool w2 = S.E % 2 == 0;
-    if (nt == 128) {
-      if (w2) PM_LAUNCH(ev, (k_answer_s<2, 128>), dim3(S.nsub), dim3(128), st, S);
-      else PM_LAUNCH(ev, (k_answer_s<1, 128>), dim3(S.nsub), dim3(128), st, S);
-    } else if (nt == 512) {
-      if (w2) PM_LAUNCH(ev, (k_answer_s<2, 512>), dim3(S.nsub), dim3(512), st, S);
-      else PM_LAUNCH(ev, (k_answer_s<1, 512>), dim3(S.nsub), dim3(512), st, S);
-    } else {
-      if (w2) PM_LAUNCH(ev, (k_answer_s<2, 256>), dim3(S.nsub), dim3(256), st, S);
-      else PM_LAUNCH(ev, (k_answer_s<1, 256>), dim3(S.nsub), dim3(256), st, S);
-    }
-    return FORM_ANSWER_S;
+  return p;
+}
+
+// With events, the launch carries them in its own dispatch packet
+// (hipExtLaunchKernelGGL): the kernel's execution time as the profiler sees it.
+#define PM_LAUNCH(kern)                                                                            \
+  do {                                                                                             \
+    if (ev.a) hipExtLaunchKernelGGL(kern, grid, blk, 0, st, ev.a, ev.b, 0, S);                      \
+    else hipLaunchKernelGGL(kern, grid, blk, 0, st, S);                                            \
+  } while (0)
+#define PM_LAUNCH_W(kern, ...)                                                                     \
+  do {                                                                                             \
+    if (S.E % 2 == 0) PM_LAUNCH((kern<2, ##__VA_ARGS__>));                                         \
+    else PM_LAUNCH((kern<1, ##__VA_ARGS__>));                                                      \
+  } while (0)
+void step_launch(hipStream_t st, const PmStep& S, const StepPlan& plan, int stage, PmEvents ev) {
+  const StepLaunch& L = plan.at[stage];
+  const dim3 grid(L.gx, L.gy), blk(L.block);
+  if (stage == STAGE_MATCH) {
+    if (L.form == MATCH_PART8) PM_LAUNCH(k_match_part8<PM_MATCHPART8_NW>);
+    else if (L.form == MATCH_PART) PM_LAUNCH(k_match_part<kMatchHints / kBlock>);
+    else PM_LAUNCH(k_match);
+    return;
   }
-  if (S.E % 2 == 0) PM_LAUNCH(ev, k_answer<2>, dim3(S.nsub), dim3(kAnsBlock), st, S);
-  else PM_LAUNCH(ev, k_answer<1>, dim3(S.nsub), dim3(kAnsBlock), st, S);
-  return FORM_ANSWER_G;
-}
-uint32_t step_gather_split(uint32_t maxSS, uint32_t nsub) {
-  if (maxSS < 256 || nsub == 0) return 1;
-  static const int forced = [] { const char* e = getenv("PM_GATHER_SPLIT"); return e ? atoi(e) : 0; }();
-  // >= 48 rows per workgroup, about 4,096 workgroups in all (two rounds of the
-  // GPU's 2,048 resident 256-thread workgroups; BIGANN-100M's 960 sub-queries:
-  // 5 ranges, 96-104 us, vs 3 ranges at ~2,048 workgroups, 124-143 us), at most
-  // 64 per sub-query; PM_GATHER_SPLIT=n forces n
-  uint32_t n = forced > 0 ? (uint32_t)forced : std::min(cdiv(maxSS, 48), cdiv(4096, nsub));
-  n = std::max(1u, std::min(n, 64u));
-  return n > 1 ? std::max(n, cdiv(maxSS, kGatherMaxRange)) : 1u;   // a range's set fits k_gather's LDS
-}
-int step_gather(hipStream_t st, const PmStep& S, PmEvents ev) {
-  const dim3 grid(S.nsplit, S.nsub);
-  if (S.E % 2 == 0) PM_LAUNCH(ev, k_gather<2>, grid, dim3(kGatherBlock), st, S);
-  else PM_LAUNCH(ev, k_gather<1>, grid, dim3(kGatherBlock), st, S);
-  return FORM_GATHER;
-}
-bool step_fused_ok(const PmStep& S, uint32_t maxPH, uint32_t max_sub_per_part) {
-  return S.args_valid && S.recg && S.err_h && max_sub_per_part <= kSpecSubs && maxPH <= kLdsPH &&
-         2 * S.nsub + S.np <= 256;
-}
-int step_fused(hipStream_t st, const PmStep& S, PmEvents ev) {
-  // S.cblk must be 1 (one match record per sub-query)
-  const dim3 grid(2 * S.nsub + S.np + S.nhelp * S.nsub);
-  if (S.E % 2 == 0) PM_LAUNCH(ev, k_step<2>, grid, dim3(kStepBlock), st, S);
-  else PM_LAUNCH(ev, k_step<1>, grid, dim3(kStepBlock), st, S);
-  return FORM_STEP;
+  switch (L.form) {
+    case FORM_STEP: PM_LAUNCH_W(k_step); break;
+    case FORM_RESOLVE_LDS: PM_LAUNCH(k_resolve<true>); break;
+    case FORM_RESOLVE_G: PM_LAUNCH(k_resolve<false>); break;
+    case FORM_MR_S2: PM_LAUNCH((k_match_resolve_s<2, 256>)); break;
+    case FORM_MR_S4: PM_LAUNCH((k_match_resolve_s<4, 256>)); break;
+    case FORM_MR_GENERAL: PM_LAUNCH(k_match_resolve<kMatchHints / kBlock>); break;
+    case FORM_GATHER: PM_LAUNCH_W(k_gather); break;
+    case FORM_ANSWER_P5: PM_LAUNCH((k_answer_p5<2, kAnsPNT>)); break;
+    case FORM_ANSWER_P: PM_LAUNCH((k_answer_p<2, kAnsPNT>)); break;
+    case FORM_ANSWER_S:
+      if (L.block == 128) PM_LAUNCH_W(k_answer_s, 128);
+      else if (L.block == 512) PM_LAUNCH_W(k_answer_s, 512);
+      else PM_LAUNCH_W(k_answer_s, 256);
+      break;
+    case FORM_ANSWER_G: PM_LAUNCH_W(k_answer); break;
+  }
 }
 uint32_t step_max_sub_per_part() { return kMaxSubPerPart; }
 uint32_t step_max_ss() { return kMaxSSLds; }

@@ -1,9 +1,9 @@
 """Every kernel form of the online query step against the oracle.
 
-Which kernels answer a step is decided by the shape predicates of
-pm_query.hip; each launcher returns the form it launched and the callers
-(engine_step, group_step_launch, the device loop through it) count it in the
-"host_path_*" counters:
+Which kernels answer a step is decided by step_plan of pm_query.hip alone
+(pm.step_plan shows its answer without a GPU: tests/test_step_plan.py); the one
+launch chain of engine_step and group_step_launch (the device loop through it)
+counts every launch by its form in the "host_path_*" counters:
 
   counter        kernel                       selected by
   step           k_step<W> (one launch)       engine_step only: descriptor in the kernel arguments (nsub <= 112,
@@ -78,6 +78,14 @@ class Case:
 
     def shape(self):   # what the inputs and the oracle's run depend on
         return (self.P, self.rows, self.E, self.F, self.qn, self.S, self.batches, self.seed)
+
+
+    def plan(self):
+        """pm.step_plan for this case's steps (host arithmetic; under the options set when it is called): an
+        engine's own step for one client, a group's shared step for several."""
+        import pacmann_amd as pm
+        return pm.step_plan(0 if self.S == 1 else 1, self.np, self.nsub, self.qn, self.geom[2], self.geom[1], self.E,
+                            no_fuse=self.fixture == "ctx_unfused")
 
 
 UNFUSED = ("match", "resolve_g", "answer_s")
@@ -242,6 +250,9 @@ def run_case(case, request, oracle):
                 assert not got[i][:, EX:].any(), (b, i)   # the words past E & ~3 stay out of the XOR
                 assert not got[i][~ok[i]].any(), (b, i)
         assert_forms(ctx, case.batches, case.forms, case.nhelp)
+        plan, counted = case.plan(), form_counts(ctx)   # the selector's own answer for the shape, without a launch
+        assert set(plan["forms"]) == {k for k in FORMS + tuple(MATCH) if counted[k]}, (plan["forms"], counted)
+        assert plan["nhelp"] * case.batches == counted["nhelp"]
         states = []
         for i, c in enumerate(clients):
             for key in ("FinishedBatchNum", "QueriesMadeInPartition", "PrepCount"):
