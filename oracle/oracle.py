@@ -40,6 +40,15 @@ class OrBatchStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class OrTrace(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "stream_pops mixed_rounds dropped_ids batch_dups batch_triples cache_hits skipped_known skipped_zero padded "
+        "tie_pushes tie_pops start_ties answer_ties max_new zero_id_positions partial_zero_lists short_starts").split()]
+
+    def asdict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 SIG = {
     "or_expand_key": (None, [C.c_char_p, u32p]),
     "or_aes128_encrypt": (None, [u32p, C.c_char_p, C.c_char_p]),
@@ -78,6 +87,7 @@ SIG = {
     "or_graph_preprocess": (None, [vp]),
     "or_search_knn": (None, [vp, f32p, C.c_int, C.c_int, C.c_int, C.c_int, i64p, i64p]),
     "or_graph_counts": (None, [vp, u64p, u64p]),
+    "or_graph_trace": (None, [vp, C.POINTER(OrTrace)]),
     "or_graph_pir": (vp, [vp]),
     "or_knn": (None, [f32p, u64, u64, f32p, u64, C.c_uint32, i64p, f32p]),
     "or_robust_prune": (None, [f32p, u64, u64, u32p, u64, u64, C.c_float, u32p, C.POINTER(C.c_uint32)]),
@@ -326,6 +336,13 @@ class Graph:
         t, s = C.c_uint64(), C.c_uint64()
         lib().or_graph_counts(self.h, C.byref(t), C.byref(s))
         return t.value, s.value
+
+    def trace(self) -> dict:
+        """Which branches this graph's searches and batch queries took so far (or_trace in pm_oracle.h):
+        counters beside the oracle's own execution of Go's order, which no result depends on."""
+        t = OrTrace()
+        lib().or_graph_trace(self.h, C.byref(t))
+        return t.asdict()
 
     def GetMetadata(self):
         return self.N, self.Dim, self.M

@@ -440,6 +440,7 @@ static const uint64_t kDefaultValue = 0xdeadbeef;                           // :
 struct or_batch {
   uint64_t E_bytes, E, N, B, P, PS, F;
   std::vector<or_pir*> sub;
+  or_trace* tr = nullptr;   // the owning graph's branch counters (or_graph_trace), if any
   uint64_t FBN = 0, QMIP = 0, Support = 0, prepCount = 0;
   double storage = 0, prepTime = 0, commOn = 0, commOff = 0;
   ~or_batch() { for (auto* s : sub) delete s; }
@@ -501,11 +502,18 @@ extern "C" int or_batch_query(or_batch* b, const uint64_t* idx, size_t n, uint64
   std::unordered_map<uint64_t, std::vector<uint64_t>> responses;
   std::vector<uint64_t> buf(E);
   for (uint64_t i = 0; i < b->P; ++i) {
+    if (b->tr && pq[i].size() > qn) b->tr->dropped_ids += pq[i].size() - qn;
     while (pq[i].size() < qn) pq[i].push_back(kDefaultValue);
     for (uint64_t j = 0; j < qn; ++j) {
       if (pq[i][j] == kDefaultValue) {
         or_pir_query(b->sub[i], 0, 0, buf.data());
       } else {
+        if (b->tr) {   // counters only
+          const or_pir* s = b->sub[i];
+          const auto before = std::count(pq[i].begin(), pq[i].begin() + j, pq[i][j]);
+          if (before) { b->tr->batch_dups++; b->tr->batch_triples += before >= 2; }
+          else if (s->FQN != s->MaxQ && s->cache.count(pq[i][j] - i * b->PS)) b->tr->cache_hits++;
+        }
         or_pir_query(b->sub[i], pq[i][j] - i * b->PS, 1, buf.data());
         responses[pq[i][j]] = buf;
       }
@@ -550,6 +558,7 @@ struct or_graph {
   or_batch* pir = nullptr;
   std::vector<Vtx> start;
   uint64_t total = 0, succ = 0;
+  or_trace tr{};   // branch counters (or_graph_trace): written, never read, by the search and the batch query
   ~or_graph() { if (pir) or_batch_free(pir); }
 };
 
@@ -575,6 +584,7 @@ extern "C" void or_graph_preprocess(or_graph* g) {
     memcpy(e + g->dim * 4, g->graph + i * g->m, g->m * 4);      // LE u32
   }
   g->pir = or_batch_new(g->n, ebytes, g->m, g->rawDB.data(), 8, g->pir_seed);
+  g->pir->tr = &g->tr;
   if (g->skipPrep) or_batch_dummy_preprocessing(g->pir); else or_batch_preprocessing(g->pir);
   // GetStartVertex: floor(sqrt(n)) distinct random ids, non-private
   uint64_t target = (uint64_t)std::sqrt((double)g->n);
@@ -646,22 +656,32 @@ extern "C" uint64_t or_graph_get_start_vertex(const or_graph* g, uint64_t cap, i
 }
 
 // container/heap (Go stdlib) on a min-heap of VD keyed by dist.
-static void heap_up(std::vector<VD>& h, int64_t j) {
-  for (;;) { int64_t i = (j - 1) / 2; if (i == j || !(h[j].dist < h[i].dist)) break; std::swap(h[i], h[j]); j = i; }
+// (`ties`, where given, counts the comparisons of two equal distances that decide a step: trace only)
+static void heap_up(std::vector<VD>& h, int64_t j, uint64_t* ties = nullptr) {
+  for (;;) {
+    int64_t i = (j - 1) / 2;
+    if (ties && i != j && h[j].dist == h[i].dist) ++*ties;
+    if (i == j || !(h[j].dist < h[i].dist)) break;
+    std::swap(h[i], h[j]); j = i;
+  }
 }
-static void heap_down(std::vector<VD>& h, int64_t i0, int64_t n) {
+static void heap_down(std::vector<VD>& h, int64_t i0, int64_t n, uint64_t* ties = nullptr) {
   int64_t i = i0;
   for (;;) {
     int64_t j1 = 2 * i + 1; if (j1 >= n || j1 < 0) break;
     int64_t j = j1, j2 = j1 + 1;
+    if (ties && j2 < n && h[j2].dist == h[j1].dist) ++*ties;
     if (j2 < n && h[j2].dist < h[j1].dist) j = j2;
+    if (ties && h[j].dist == h[i].dist) ++*ties;
     if (!(h[j].dist < h[i].dist)) break;
     std::swap(h[i], h[j]); i = j;
   }
 }
-static void heap_push(std::vector<VD>& h, VD x) { h.push_back(x); heap_up(h, (int64_t)h.size() - 1); }
-static VD heap_pop(std::vector<VD>& h) {
-  int64_t n = (int64_t)h.size() - 1; std::swap(h[0], h[n]); heap_down(h, 0, n);
+static void heap_push(std::vector<VD>& h, VD x, uint64_t* ties = nullptr) {
+  h.push_back(x); heap_up(h, (int64_t)h.size() - 1, ties);
+}
+static VD heap_pop(std::vector<VD>& h, uint64_t* ties = nullptr) {
+  int64_t n = (int64_t)h.size() - 1; std::swap(h[0], h[n]); heap_down(h, 0, n, ties);
   VD r = h.back(); h.pop_back(); return r;
 }
 
@@ -675,44 +695,58 @@ extern "C" void or_search_knn(or_graph* g, const float* query, int k, int max_st
   std::unordered_map<int64_t, Vtx> known;
   std::unordered_map<int64_t, float> kdist;
   std::vector<VD> heap;
+  or_trace& tr = g->tr;
   if (!benchmarking) {
     std::vector<std::pair<VD, size_t>> fs;
     for (size_t i = 0; i < g->start.size(); ++i)
       fs.push_back({{or_l2dist(g->start[i].vec.data(), query, g->dim), g->start[i].id}, i});
+    tr.short_starts += (int64_t)fs.size() < parallel;
     std::stable_sort(fs.begin(), fs.end(), [](const auto& a, const auto& b) { return a.first.dist < b.first.dist; });
     for (size_t i = 0; (int64_t)heap.size() < parallel && i < fs.size(); ++i) {
       int64_t id = fs[i].first.id;
       if (known.count(id)) continue;
       known[id] = g->start[fs[i].second];
       kdist[id] = fs[i].first.dist;
-      heap_push(heap, fs[i].first);
+      heap_push(heap, fs[i].first, &tr.tie_pushes);
       reach[id] = 0;
+      if (i + 1 < fs.size() && fs[i + 1].first.dist == fs[i].first.dist) tr.start_ties++;
     }
   }
   for (int step = 0; step < max_step; ++step) {
     std::vector<int64_t> batch;
+    uint64_t from_stream = 0, from_heap = 0, fresh = 0;
     for (int r = 0; r < parallel; ++r) {
       if (heap.empty() || benchmarking) {
         for (int64_t i = 0; i < m; ++i) batch.push_back((int64_t)g->rng.intn((uint64_t)n));
+        from_stream++;
       } else {
-        VD it = heap_pop(heap);
+        VD it = heap_pop(heap, &tr.tie_pops);
         const Vtx& v = known[it.id];
         batch.insert(batch.end(), v.nb.begin(), v.nb.end());
+        from_heap++;
       }
+    }
+    if (!benchmarking) {
+      tr.stream_pops += from_stream;
+      tr.mixed_rounds += from_stream && from_heap;
+      for (int64_t x : batch) tr.zero_id_positions += x == 0;
     }
     std::vector<Vtx> res = get_vertex_info(g, batch);
     if (benchmarking) continue;
     for (auto& v : res) {
-      if (known.count(v.id)) continue;
+      if (known.count(v.id)) { tr.skipped_known++; continue; }
       bool ok = false;
       for (auto x : v.nb) if (x != 0) { ok = true; break; }
+      if (!ok) tr.skipped_zero++;
       if (ok) {
+        for (auto x : v.nb) if (x == 0) { tr.partial_zero_lists++; break; }
+        tr.max_new = std::max<uint64_t>(tr.max_new, ++fresh);
         float d = or_l2dist(v.vec.data(), query, g->dim);
         int64_t id = v.id;
         reach[id] = step;
         kdist[id] = d;
         known[id] = std::move(v);
-        heap_push(heap, {d, id});
+        heap_push(heap, {d, id}, &tr.tie_pushes);
       }
     }
   }
@@ -721,10 +755,14 @@ extern "C" void or_search_knn(or_graph* g, const float* query, int k, int max_st
   std::sort(all.begin(), all.end(), [](const VD& a, const VD& b) {
     return a.dist < b.dist || (a.dist == b.dist && a.id < b.id); });
   for (int i = 0; i < k; ++i) {
-    if (i >= (int)all.size()) { ids_out[i] = -1; steps_out[i] = -1; }
-    else { ids_out[i] = all[i].id; steps_out[i] = reach[all[i].id]; }
+    if (i >= (int)all.size()) { ids_out[i] = -1; steps_out[i] = -1; tr.padded++; }
+    else {
+      ids_out[i] = all[i].id; steps_out[i] = reach[all[i].id];
+      if (i + 1 < (int)all.size() && all[i + 1].dist == all[i].dist) tr.answer_ties++;
+    }
   }
 }
+extern "C" void or_graph_trace(const or_graph* g, or_trace* t) { *t = g->tr; }
 extern "C" void or_graph_counts(const or_graph* g, uint64_t* total, uint64_t* succ) {
   *total = g->total; *succ = g->succ;
 }

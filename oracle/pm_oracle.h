@@ -103,6 +103,29 @@ void     or_graph_preprocess(or_graph*);            /* GraphANNFrontend.Preproce
 void     or_search_knn(or_graph*, const float* query, int k, int max_step, int parallel,
                        int benchmarking, int64_t* ids_out, int64_t* steps_out);
 void     or_graph_counts(const or_graph*, uint64_t* total, uint64_t* succ);
+/* Which branches the graph's searches and batch queries took so far (counters
+ * only: no result depends on them).  Rounds are SearchKNN steps; a kept id is
+ * one of the first queryNumToMake ids of its partition in a batch. */
+typedef struct {
+  uint64_t stream_pops;      /* pops that found the heap empty: m ids of the id stream        */
+  uint64_t mixed_rounds;     /* rounds with heap pops and stream pops                          */
+  uint64_t dropped_ids;      /* ids past queryNumToMake in their partition (batch-pir.go:195)  */
+  uint64_t batch_dups;       /* kept ids equal to an earlier kept id of the same batch         */
+  uint64_t batch_triples;    /* ... of them, those equal to two or more earlier kept ids       */
+  uint64_t cache_hits;       /* other kept ids answered from the localCache (pir.go:380)       */
+  uint64_t skipped_known;    /* positions skipped as already known (search.go:186)             */
+  uint64_t skipped_zero;     /* positions skipped for an all-zero neighbour list               */
+  uint64_t padded;           /* answer slots padded with -1                                    */
+  uint64_t tie_pushes;       /* heap.Push: up() stopped at a parent of equal distance          */
+  uint64_t tie_pops;         /* heap.Pop: down() compared two equal distances                  */
+  uint64_t start_ties;       /* chosen start vertices whose successor in the sort has their distance */
+  uint64_t answer_ties;      /* answered ids whose successor in the final sort has their distance */
+  uint64_t max_new;          /* the largest number of new vertices in one round                */
+  uint64_t zero_id_positions;  /* batch positions holding vertex 0                             */
+  uint64_t partial_zero_lists; /* new vertices whose neighbour list holds a 0                  */
+  uint64_t short_starts;       /* queries whose start set is smaller than `parallel`           */
+} or_trace;
+void     or_graph_trace(const or_graph*, or_trace*);
 or_batch* or_graph_pir(or_graph*);
 /* private-search.go:220-233 query loop incl. maintenance trigger; times in s */
 void     or_search_loop(or_graph*, const float* queries, uint64_t q, int k, int step,

@@ -14,7 +14,11 @@
 // path (no partition at its query budget, no batch-layer re-preprocessing);
 // otherwise, or with pm_set_option("device_loop", 0) / PM_DEVICE_LOOP=0, the
 // host loop serves the call.  Every session's answers, counters and state
-// equal the host loop's (tests/test_gpu_parity.py, test_gpu_headline.py).
+// equal the host loop's and the oracle's: every branch of the round kernel
+// and every limit of drl_plan at its smallest shape in
+// tests/test_gpu_devloop_rounds.py (cases and the oracle's evidence that each
+// reaches its branch: tests/devloop_cases.py, test_devloop_cases.py), the
+// headline shape in tests/test_gpu_parity.py and test_gpu_headline.py.
 static bool device_loop_on() {
   const int o = g_device_loop.load();
   if (o >= 0) return o != 0;

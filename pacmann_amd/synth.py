@@ -71,6 +71,59 @@ def random_graph(n, m, seed=0):
     return g.astype(np.uint32)
 
 
+def lone_id_lists(g, every, seed=0):
+    """A copy of graph g with every `every`-th vertex's list (from vertex every / 2) all zero but for one
+    non-zero id in a random column: whether such a list is empty, or equals the true one, is decided by a
+    single word anywhere in it."""
+    g = g.copy()
+    n, m = g.shape
+    rng = np.random.default_rng([seed, 2])
+    u = np.arange(every // 2, n, every)
+    one = g[u, 0].copy()
+    one[one == 0] = 1
+    g[u] = 0
+    g[u, rng.integers(0, m, size=len(u))] = one
+    return g
+
+
+def windowed_graph(n, m, w, seed=0):
+    """Neighbours of u drawn (with repeats) from [u - w, u + w] mod n without u.  With w about m the vertices
+    a search pops share neighbours, ids come back round after round, and a batch crowds one or two batch-PIR
+    partitions: in-batch repeats, known and cached ids and dropped ids all at once."""
+    rng = np.random.default_rng(seed)
+    off = np.concatenate([np.arange(-w, 0), np.arange(1, w + 1)])
+    return ((np.arange(n)[:, None] + off[rng.integers(0, 2 * w, size=(n, m))]) % n).astype(np.uint32)
+
+
+def sparse_graph(n, m, keep, seed=0):
+    """random_graph in which only a fraction `keep` of the vertices have a neighbour list; the others' rows
+    are all zero, so a search skips them and its heap runs dry (keep = 0: no vertex is ever added)."""
+    g = random_graph(n, m, seed)
+    kept = np.random.default_rng([seed, 1]).random(n) < keep
+    g[~kept] = 0
+    return g
+
+
+def vertex0_graph(n, m, seed=0):
+    """random_graph with vertex 0 in one column of every second vertex's list, and every eighth vertex's
+    list all zero but for one id: id 0 as a vertex, as a neighbour, and lists that are zero only in part."""
+    g = random_graph(n, m, seed)
+    rng = np.random.default_rng([seed, 3])
+    u = np.arange(1, n, 2)
+    g[u, rng.integers(0, m, size=len(u))] = 0
+    return lone_id_lists(g, 8, seed)
+
+
+def tied_vectors(n, dim, distinct, seed=0):
+    """(rows [n, dim], prototypes [distinct, dim]): integer-valued rows, each one of `distinct` prototypes
+    (every prototype n / distinct times, shuffled), so that many distances to a query are exactly equal;
+    the prototypes themselves serve as queries."""
+    rng = np.random.default_rng(seed)
+    protos = rng.integers(0, 4, size=(distinct, dim)).astype(np.float32)
+    lab = rng.permutation(np.arange(n) % distinct)
+    return protos[lab], protos
+
+
 def msmarco_like_vectors(n, d=192, seed=0, sigma_hi=0.82, sigma_lo=0.29, latent=16, centers=256, block=1 << 17):
     """MS-MARCO-shaped stand-in: the reference's corpus is
     768-d TAS-B embeddings reduced to 192 dims by PCA
