@@ -499,6 +499,44 @@ int pm_build_graph(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, 
  * from the brute-force kernel.  Other arguments as pm_build_graph. */
 int pm_build_graph_exact(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
                          uint64_t seed, uint32_t* graph, double* times, uint64_t* fallback_rows);
+/* Test probes of the two calls above (tests/test_gpu_knn_stages.py,
+ * tests/test_gpu_prune.py): the same uploads and kernel launches, with the
+ * values the product drops copied out.
+ * pm_knn_stages runs pm_knn (exact = 0) or pm_knn_exact (exact != 0) for k and
+ * returns, per query row, the prefilter's 64 candidate ids in key order (cand
+ * nq x 64, 0xffffffff for an empty slot) and their prefilter distances (pref
+ * nq x 64, all-ones bits for an empty slot); both are required.  For exact it
+ * also fills whichever of these is not NULL: tau [nq] (the 64th prefilter
+ * distance; NaN bits with fewer than 64 base rows), eps [nq] (the bound the
+ * row was judged with; NaN bits for n <= 64, where no row is judged), qnorm
+ * [nq] and bnorm [n] (the norms), maxnorm (the bits of the largest base norm),
+ * bhi / blo (the bf16 halves of the base rows, n x dp, zero padded),
+ * uncertified [nq] (the rows that went to the brute-force kernel, ascending;
+ * their number in n_uncertified = pm_knn_exact's fallback_rows).  dp: the
+ * padded row width (128 or 192).  PM_EINVAL as pm_knn_exact, and for nq = 0. */
+typedef struct pm_knn_stages_out {
+  uint32_t* cand;
+  float* pref;
+  float *tau, *eps, *qnorm, *bnorm;
+  uint32_t* maxnorm;
+  uint16_t *bhi, *blo;
+  uint64_t* uncertified;
+  uint64_t n_uncertified;
+  uint32_t dp;
+} pm_knn_stages_out;
+int pm_knn_stages(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                  uint32_t k, int exact, pm_knn_stages_out* out);
+/* pm_robust_prune runs robustPrune (build_graph.go:169-236) on the GPU as the
+ * build's second pass does: list b is ids[offs[b] .. offs[b] + lens[b]), the
+ * candidates of vertex verts[b] (distinct vertices, ids < n; nids entries in
+ * ids).  presorted = 0: every list by the kernel's own sort, which holds 4,096
+ * candidates; a longer list sets *err to 1 and gets length 0.  presorted != 0:
+ * every list by the form the build uses for longer lists (distances on the
+ * GPU, sorted on the host, the same greedy pass).  out: nverts x m (row b holds
+ * out_len[b] ids).  m <= 64, dim <= 256. */
+int pm_robust_prune(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* verts,
+                    uint64_t nverts, const uint64_t* offs, const uint32_t* lens, const uint32_t* ids, uint64_t nids,
+                    uint32_t m, float alpha, int presorted, uint32_t* out, uint32_t* out_len, uint32_t* err);
 
 #ifdef __cplusplus
 }

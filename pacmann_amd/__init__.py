@@ -73,6 +73,12 @@ class StepForms(C.Structure):   # pm_step_forms
         [(n, C.c_uint32) for n in "nhelp nsplit qw np_live cblk no_guess qset args_valid".split()]
 
 
+class KnnStagesOut(C.Structure):   # pm_knn_stages_out
+    _fields_ = [("cand", u32p), ("pref", f32p), ("tau", f32p), ("eps", f32p), ("qnorm", f32p), ("bnorm", f32p),
+                ("maxnorm", u32p), ("bhi", C.POINTER(C.c_uint16)), ("blo", C.POINTER(C.c_uint16)),
+                ("uncertified", u64p), ("n_uncertified", u64), ("dp", C.c_uint32)]
+
+
 # pm_combine_fn (include/pacmann.h): (user, team, dev_words, nwords, stream) -> 0 on success
 COMBINE_FN = C.CFUNCTYPE(C.c_int, vp, C.c_uint32, vp, u64, vp)
 
@@ -132,6 +138,9 @@ SIGNATURES = {
     "pm_build_graph": (C.c_int, [vp, f32p, u64, u64, u64, C.c_float, u64, u32p, C.POINTER(dbl)]),
     "pm_knn_exact": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, i64p, f32p, u64p]),
     "pm_build_graph_exact": (C.c_int, [vp, f32p, u64, u64, u64, C.c_float, u64, u32p, C.POINTER(dbl), u64p]),
+    "pm_knn_stages": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, C.c_int, C.POINTER(KnnStagesOut)]),
+    "pm_robust_prune": (C.c_int, [vp, f32p, u64, u64, u32p, u64, u64p, u32p, u32p, u64, C.c_uint32, C.c_float, C.c_int,
+                                  u32p, u32p, u32p]),
     "pm_search_loop_sessions": (C.c_int, [C.POINTER(vp), C.c_uint32, f32p, u64, C.c_int, C.c_int, C.c_int,
                                           i64p, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "pm_batchpir_group_create": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
@@ -896,6 +905,55 @@ def knn_exact(base, queries, k: int, ctx: Context | None = None, with_dist: bool
     _check(lib().pm_knn_exact(ctx.h, _p(b, f32p), b.shape[0], b.shape[1], _p(q, f32p), q.shape[0], k, _p(ids, i64p),
                               _p(d, f32p), C.byref(fb)))
     return (ids, d, int(fb.value)) if with_dist else (ids, int(fb.value))
+
+
+def knn_stages(base, queries, k: int, ctx: Context | None = None, exact: bool = True) -> dict:
+    """pm_knn_stages: what pm.knn (exact=False) or pm.knn_exact keeps inside for
+    these rows.  "cand" [nq, 64] uint32 (0xffffffff: empty slot) and "pref"
+    [nq, 64] float32, the prefilter's keys in order, and "dp"; exact adds "tau",
+    "eps", "qnorm" [nq], "bnorm" [n], "maxnorm" (bits), "bhi" / "blo" [n, dp]
+    uint16 and "uncertified" (ascending row numbers)."""
+    ctx = ctx or default_context()
+    b = np.ascontiguousarray(base, dtype=np.float32)
+    q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, b.shape[1])
+    n, nq, dp = b.shape[0], q.shape[0], 192 if b.shape[1] > 128 else 128
+    r = {"cand": np.zeros((nq, 64), np.uint32), "pref": np.zeros((nq, 64), np.float32)}
+    if exact:
+        r.update(tau=np.zeros(nq, np.float32), eps=np.zeros(nq, np.float32), qnorm=np.zeros(nq, np.float32),
+                 bnorm=np.zeros(n, np.float32), maxnorm=np.zeros(1, np.uint32), bhi=np.zeros((n, dp), np.uint16),
+                 blo=np.zeros((n, dp), np.uint16), uncertified=np.zeros(nq, np.uint64))
+    o = KnnStagesOut()
+    for name, ctype in KnnStagesOut._fields_:
+        if name in r:
+            setattr(o, name, _p(r[name], ctype))
+    _check(lib().pm_knn_stages(ctx.h, _p(b, f32p), n, b.shape[1], _p(q, f32p), nq, k, int(exact), C.byref(o)))
+    assert o.dp == dp
+    r["dp"] = dp
+    if exact:
+        r["uncertified"] = r["uncertified"][:o.n_uncertified]
+        r["maxnorm"] = int(r["maxnorm"][0])
+    return r
+
+
+def robust_prune(vectors, verts, lists, m: int, alpha: float = 1.2, presorted: bool = False,
+                 ctx: Context | None = None):
+    """pm_robust_prune: robustPrune of lists[b], the candidates of vertex
+    verts[b] (distinct), on the GPU.  Returns (one uint32 array per list, err)."""
+    ctx = ctx or default_context()
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    vs = np.ascontiguousarray(verts, dtype=np.uint32).ravel()
+    lens = np.array([len(x) for x in lists], dtype=np.uint32)
+    offs = np.zeros(len(lens) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(lens, dtype=np.uint64)
+    ids = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.uint32) for x in lists] or
+                                              [np.zeros(0, np.uint32)]), dtype=np.uint32)
+    out = np.zeros((len(vs), m), dtype=np.uint32)
+    ol = np.zeros(len(vs), dtype=np.uint32)
+    err = np.zeros(1, dtype=np.uint32)
+    _check(lib().pm_robust_prune(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], _p(vs, u32p), len(vs), _p(offs, u64p),
+                                 _p(lens, u32p), _p(ids, u32p), len(ids), m, alpha, int(presorted), _p(out, u32p),
+                                 _p(ol, u32p), _p(err, u32p)))
+    return [out[b, :ol[b]].copy() for b in range(len(vs))], int(err[0])
 
 
 def build_graph(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context | None = None,

@@ -56,7 +56,15 @@ static int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDe
 // re-rank; exact: the three-product prefilter, the certificate in the re-rank
 // and the brute-force pass over the rows it did not certify, whose number goes
 // to *fallback (pm_knn_exact).  Enqueued on c->stream; exact synchronises it.
-struct KnnOut { DevBuf cand, out, dist, len; };
+// stages (pm_knn_stages): the kernels also store what they otherwise drop: the
+// candidates' prefilter distances (pref [nq][64]) and, exact, each row's eps
+// (NaN bits where no row was judged: n <= 64); tau and the uncertified list
+// (nl rows, unordered) stay in the struct either way.
+struct KnnOut {
+  DevBuf cand, out, dist, len, tau, list, nlist, pref, eps;
+  bool stages = false;
+  uint64_t nl = 0;
+};
 static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, uint64_t nq, uint32_t dim, uint32_t K,
                       bool self_base, bool want_dist, bool exact, KnnOut& o, uint64_t* fallback) {
   hipStream_t st = c->stream;
@@ -64,34 +72,42 @@ static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, u
   CHK(o.out.reserve(std::max<uint64_t>(4, nq * K * 4)));
   if (want_dist) CHK(o.dist.reserve(std::max<uint64_t>(4, nq * K * 4)));
   CHK(o.len.reserve(std::max<uint64_t>(4, nq * 4)));
+  if (o.stages) CHK(o.pref.reserve(std::max<uint64_t>(4, nq * pmk::knn_top() * 4)));
+  uint32_t* pref = o.stages ? o.pref.as<uint32_t>() : nullptr;
   const double pre_bytes = (double)nq * n * B.dp * 2, rr_bytes = (double)nq * pmk::knn_top() * dim * 4;
   if (!exact) {
     c->timed("knn_prefilter", pre_bytes, [&] {
-      pmk::knn_prefilter(st, B.xb.p, B.xn.as<float>(), n, Q.xb.p, Q.xn.as<float>(), nq, B.dp, o.cand.as<uint32_t>()); });
+      pmk::knn_prefilter(st, B.xb.p, B.xn.as<float>(), n, Q.xb.p, Q.xn.as<float>(), nq, B.dp, o.cand.as<uint32_t>(),
+                         pref); });
     c->timed("knn_rerank", rr_bytes, [&] {
       pmk::knn_rerank(st, B.x.as<float>(), n, dim, Q.x.as<float>(), nq, o.cand.as<uint32_t>(), K, self_base,
                       o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>()); });
     return 0;
   }
-  DevBuf tau, list, nlist;
-  CHK(tau.reserve(std::max<uint64_t>(4, nq * 4)));
-  CHK(list.reserve(std::max<uint64_t>(8, nq * 8)));
-  CHK(nlist.reserve(8));
-  HIPCHK(hipMemsetAsync(nlist.p, 0, 8, st));
+  CHK(o.tau.reserve(std::max<uint64_t>(4, nq * 4)));
+  CHK(o.list.reserve(std::max<uint64_t>(8, nq * 8)));
+  CHK(o.nlist.reserve(8));
+  HIPCHK(hipMemsetAsync(o.nlist.p, 0, 8, st));
+  if (o.stages) {
+    CHK(o.eps.reserve(std::max<uint64_t>(4, nq * 4)));
+    HIPCHK(hipMemsetAsync(o.eps.p, 0xff, std::max<uint64_t>(4, nq * 4), st));
+  }
   c->timed("knn_prefilter_x3", 2 * pre_bytes, [&] {
     pmk::knn_prefilter_x3(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
-                          o.cand.as<uint32_t>(), tau.as<float>()); });
+                          o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
   c->timed("knn_rerank", rr_bytes, [&] {
     pmk::knn_rerank_cert(st, B.x.as<float>(), n, dim, Q.x.as<float>(), nq, o.cand.as<uint32_t>(), K, self_base,
                          o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>(), Q.xn.as<float>(),
-                         tau.as<float>(), B.mx.as<uint32_t>(), B.dp, list.as<uint64_t>(), nlist.as<uint64_t>()); });
+                         o.tau.as<float>(), B.mx.as<uint32_t>(), B.dp, o.list.as<uint64_t>(), o.nlist.as<uint64_t>(),
+                         o.stages ? o.eps.as<float>() : nullptr); });
   uint64_t nl = 0;
-  HIPCHK(hipMemcpyAsync(&nl, nlist.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&nl, o.nlist.p, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   c->timed("knn_brute", (double)nl * n * dim * 4, [&] {
-    pmk::knn_brute(st, B.x.as<float>(), n, dim, Q.x.as<float>(), list.as<uint64_t>(), nl, K, self_base,
+    pmk::knn_brute(st, B.x.as<float>(), n, dim, Q.x.as<float>(), o.list.as<uint64_t>(), nl, K, self_base,
                    o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>()); });
-  HIPCHK(hipStreamSynchronize(st));   // list and tau are freed on return
+  HIPCHK(hipStreamSynchronize(st));
+  o.nl = nl;
   if (fallback) *fallback = nl;
   return 0;
 }
@@ -133,6 +149,126 @@ extern "C" int pm_knn_exact(pm_ctx* c, const float* base, uint64_t n, uint64_t d
                             uint64_t nq, uint32_t k, int64_t* ids, float* dists, uint64_t* fallback_rows) {
   if (fallback_rows) *fallback_rows = 0;
   return knn_impl(c, base, n, dim, queries, nq, k, ids, dists, true, fallback_rows);
+}
+
+// pm_knn_stages: pm_knn's (exact: pm_knn_exact's) own upload and launches
+// (knn_upload, knn_device), with the intermediate values copied out.
+extern "C" int pm_knn_stages(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries,
+                             uint64_t nq, uint32_t k, int exact, pm_knn_stages_out* out) {
+  if (!c || !base || !queries || !out || !out->cand || !out->pref) return fail(PM_EINVAL, "NULL argument");
+  if (k == 0 || k > pmk::knn_top()) return fail(PM_EINVAL, "k must be in [1, 64]");
+  if (n == 0 || dim == 0 || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be in [1, 2^32-1)");
+  if (nq == 0) return fail(PM_EINVAL, "nq must be > 0");
+  if (!pmk::knn_pad_dim((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)))
+    return fail(PM_EINVAL, "kNN supports dim <= 192");
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  KnnDev B, Q;
+  CHK(knn_upload(c, base, n, (uint32_t)dim, B, exact != 0));
+  CHK(knn_upload(c, queries, nq, (uint32_t)dim, Q, exact != 0));
+  KnnOut o;
+  o.stages = true;
+  CHK(knn_device(c, B, n, Q, nq, (uint32_t)dim, k, false, true, exact != 0, o, nullptr));
+  auto get = [&](void* dst, const DevBuf& src, uint64_t bytes) {
+    return dst ? hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+  };
+  const uint64_t top = pmk::knn_top();
+  out->dp = B.dp;
+  out->n_uncertified = 0;
+  HIPCHK(get(out->cand, o.cand, nq * top * 4));
+  HIPCHK(get(out->pref, o.pref, nq * top * 4));
+  std::vector<uint64_t> list;
+  if (exact) {
+    HIPCHK(get(out->tau, o.tau, nq * 4));
+    HIPCHK(get(out->eps, o.eps, nq * 4));
+    HIPCHK(get(out->qnorm, Q.xn, nq * 4));
+    HIPCHK(get(out->bnorm, B.xn, n * 4));
+    HIPCHK(get(out->maxnorm, B.mx, 4));
+    HIPCHK(get(out->bhi, B.xb, n * B.dp * 2));
+    HIPCHK(get(out->blo, B.xl, n * B.dp * 2));
+    list.resize(o.nl);
+    if (o.nl) HIPCHK(hipMemcpyAsync(list.data(), o.list.p, o.nl * 8, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  if (exact) {
+    std::sort(list.begin(), list.end());   // the kernel appends in any order
+    out->n_uncertified = list.size();
+    if (out->uncertified) std::copy(list.begin(), list.end(), out->uncertified);
+  }
+  return 0;
+}
+
+// robustPrune on the GPU of the listed vertices' lists (the second pass of the
+// build, :464-466; pm_robust_prune): vertex u's candidates are conn[coff[u] ..
+// coff[u] + clen[u]), X the device rows.  big: by k_prune's own LDS sort (lists
+// up to prune_max_list()).  huge: lists above the kernel's LDS sort (hub
+// vertices: every in-edge of a popular vertex is kept, :448-462 sample by the
+// TARGET's inbounds) get their candidate distances on the GPU (k_cand_dist),
+// their (L2Dist, position) order by a host sort of those exact keys, and the
+// same greedy pass (presorted k_prune).  P [n][m] and PL [n] hold the listed
+// vertices' results; *e the kernel's error flag (a big list above the limit).
+static int prune_lists(pm_ctx* c, const float* X, uint64_t n, uint32_t dim, const std::vector<uint32_t>& big,
+                       const std::vector<uint32_t>& huge, const std::vector<uint64_t>& coff,
+                       const std::vector<uint32_t>& clen, const std::vector<uint32_t>& conn, uint32_t m, float alpha,
+                       std::vector<uint32_t>& P, std::vector<uint32_t>& PL, uint32_t* e) {
+  *e = 0;
+  if (big.empty() && huge.empty()) return 0;
+  hipStream_t st = c->stream;
+  DevBuf dv, dh, doff, dlen, dids, dout, dol, dd, dpos, err;
+  CHK(dv.reserve(std::max<size_t>(1, big.size()) * 4));
+  CHK(dh.reserve(std::max<size_t>(1, huge.size()) * 4));
+  CHK(doff.reserve(n * 8));
+  CHK(dlen.reserve(n * 4));
+  CHK(dids.reserve(std::max<uint64_t>(4, conn.size() * 4)));
+  CHK(dout.reserve(n * m * 4));
+  CHK(dol.reserve(n * 4));
+  CHK(err.reserve(4));
+  HIPCHK(hipMemsetAsync(err.p, 0, 4, st));
+  if (!big.empty()) HIPCHK(hipMemcpyAsync(dv.p, big.data(), big.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(doff.p, coff.data(), n * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(dlen.p, clen.data(), n * 4, hipMemcpyHostToDevice, st));
+  if (!conn.empty()) HIPCHK(hipMemcpyAsync(dids.p, conn.data(), conn.size() * 4, hipMemcpyHostToDevice, st));
+  c->timed("prune", 0.0, [&] {
+    pmk::prune(st, X, dim, dv.as<uint32_t>(), big.size(), doff.as<uint64_t>(), 0, dlen.as<uint32_t>(),
+               dids.as<uint32_t>(), m, alpha, dout.as<uint32_t>(), dol.as<uint32_t>(), err.as<uint32_t>()); });
+  if (!huge.empty()) {
+    CHK(dd.reserve(std::max<uint64_t>(4, conn.size() * 4)));
+    CHK(dpos.reserve(std::max<uint64_t>(4, conn.size() * 4)));
+    HIPCHK(hipMemcpyAsync(dh.p, huge.data(), huge.size() * 4, hipMemcpyHostToDevice, st));
+    pmk::cand_dist(st, X, dim, dh.as<uint32_t>(), huge.size(), doff.as<uint64_t>(), dlen.as<uint32_t>(),
+                   dids.as<uint32_t>(), dd.as<float>());
+    std::vector<float> hd(conn.size());
+    if (!conn.empty()) HIPCHK(hipMemcpyAsync(hd.data(), dd.p, conn.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<uint32_t> pos(conn.size());
+    par_for(huge.size(), [&](uint64_t a, uint64_t b) {
+      std::vector<uint64_t> key;
+      for (uint64_t i = a; i < b; ++i) {   // sort.Slice by distance; ties by position (as the LDS sort)
+        const uint32_t u = huge[i];
+        const uint64_t o = coff[u], len = clen[u];
+        key.resize(len);
+        for (uint64_t j = 0; j < len; ++j) {
+          uint32_t bits;
+          memcpy(&bits, &hd[o + j], 4);
+          key[j] = ((uint64_t)bits << 32) | j;
+        }
+        std::sort(key.begin(), key.end());
+        for (uint64_t j = 0; j < len; ++j) pos[o + j] = (uint32_t)key[j];
+      }
+    });
+    if (!pos.empty()) HIPCHK(hipMemcpyAsync(dpos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, st));
+    c->timed("prune", 0.0, [&] {
+      pmk::prune(st, X, dim, dh.as<uint32_t>(), huge.size(), doff.as<uint64_t>(), 0, dlen.as<uint32_t>(),
+                 dids.as<uint32_t>(), m, alpha, dout.as<uint32_t>(), dol.as<uint32_t>(), err.as<uint32_t>(),
+                 dpos.as<uint32_t>(), dd.as<float>()); });
+  }
+  P.resize(n * m);
+  PL.resize(n);
+  HIPCHK(hipMemcpyAsync(P.data(), dout.p, n * m * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(PL.data(), dol.p, n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(e, err.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
 }
 
 // pm_build_graph and pm_build_graph_exact
@@ -217,69 +353,16 @@ static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_
       visit(u, [&](uint64_t j, uint32_t v) { if (keep(u, j, v)) *o++ = v; });
     }
   });
-  // second pass: robustPrune of the lists above m (:464-466) on the GPU.  Lists
-  // above the kernel's LDS sort (hub vertices: every in-edge of a popular
-  // vertex is kept, :448-462 sample by the TARGET's inbounds) get their
-  // candidate distances on the GPU, their (L2Dist, position) order by a host
-  // sort of those exact keys, and the same greedy pass (presorted k_prune).
+  // second pass: robustPrune of the lists above m (:464-466) on the GPU
+  // (prune_lists), those above the kernel's LDS sort presorted
   std::vector<uint32_t> big, huge;
   for (uint64_t u = 0; u < n; ++u)
     if (clen2[u] > pmk::prune_max_list()) huge.push_back((uint32_t)u);
     else if (clen2[u] > m) big.push_back((uint32_t)u);
   auto t3 = Clock::now();
   if (!big.empty() || !huge.empty()) {
-    DevBuf dv, dh, doff, dlen, dids, dout, dol, dd, dpos;
-    CHK(dv.reserve(std::max<size_t>(1, big.size()) * 4));
-    CHK(dh.reserve(std::max<size_t>(1, huge.size()) * 4));
-    CHK(doff.reserve(n * 8));
-    CHK(dlen.reserve(n * 4));
-    CHK(dids.reserve(std::max<uint64_t>(4, conn.size() * 4)));
-    CHK(dout.reserve(n * m * 4));
-    CHK(dol.reserve(n * 4));
-    if (!big.empty()) HIPCHK(hipMemcpyAsync(dv.p, big.data(), big.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(doff.p, coff.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dlen.p, clen2.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(dids.p, conn.data(), conn.size() * 4, hipMemcpyHostToDevice, st));
-    c->timed("prune", 0.0, [&] {
-      pmk::prune(st, X.x.as<float>(), (uint32_t)dim, dv.as<uint32_t>(), big.size(), doff.as<uint64_t>(), 0,
-                 dlen.as<uint32_t>(), dids.as<uint32_t>(), (uint32_t)m, alpha, dout.as<uint32_t>(),
-                 dol.as<uint32_t>(), err.as<uint32_t>()); });
-    if (!huge.empty()) {
-      CHK(dd.reserve(conn.size() * 4));
-      CHK(dpos.reserve(conn.size() * 4));
-      HIPCHK(hipMemcpyAsync(dh.p, huge.data(), huge.size() * 4, hipMemcpyHostToDevice, st));
-      pmk::cand_dist(st, X.x.as<float>(), (uint32_t)dim, dh.as<uint32_t>(), huge.size(), doff.as<uint64_t>(),
-                     dlen.as<uint32_t>(), dids.as<uint32_t>(), dd.as<float>());
-      std::vector<float> hd(conn.size());
-      HIPCHK(hipMemcpyAsync(hd.data(), dd.p, conn.size() * 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      std::vector<uint32_t> pos(conn.size());
-      par_for(huge.size(), [&](uint64_t a, uint64_t b) {
-        std::vector<uint64_t> key;
-        for (uint64_t i = a; i < b; ++i) {   // sort.Slice by distance; ties by position (as the LDS sort)
-          const uint32_t u = huge[i];
-          const uint64_t o = coff[u], len = clen2[u];
-          key.resize(len);
-          for (uint64_t j = 0; j < len; ++j) {
-            uint32_t bits;
-            memcpy(&bits, &hd[o + j], 4);
-            key[j] = ((uint64_t)bits << 32) | j;
-          }
-          std::sort(key.begin(), key.end());
-          for (uint64_t j = 0; j < len; ++j) pos[o + j] = (uint32_t)key[j];
-        }
-      });
-      HIPCHK(hipMemcpyAsync(dpos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, st));
-      c->timed("prune", 0.0, [&] {
-        pmk::prune(st, X.x.as<float>(), (uint32_t)dim, dh.as<uint32_t>(), huge.size(), doff.as<uint64_t>(), 0,
-                   dlen.as<uint32_t>(), dids.as<uint32_t>(), (uint32_t)m, alpha, dout.as<uint32_t>(),
-                   dol.as<uint32_t>(), err.as<uint32_t>(), dpos.as<uint32_t>(), dd.as<float>()); });
-    }
-    std::vector<uint32_t> P(n * m), PL(n);
-    HIPCHK(hipMemcpyAsync(P.data(), dout.p, n * m * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(PL.data(), dol.p, n * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&e, err.p, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    std::vector<uint32_t> P, PL;
+    CHK(prune_lists(c, X.x.as<float>(), n, (uint32_t)dim, big, huge, coff, clen2, conn, (uint32_t)m, alpha, P, PL, &e));
     if (e) return fail(PM_EINVAL, "robustPrune: a connection list above the kernel's limit");
     for (const auto* lst : {&big, &huge})
       for (uint32_t u : *lst) {   // robustPrune of a list > m returns exactly m
@@ -320,4 +403,47 @@ extern "C" int pm_build_graph_exact(pm_ctx* c, const float* vectors, uint64_t n,
                                     uint64_t* fallback_rows) {
   if (fallback_rows) *fallback_rows = 0;
   return build_graph_impl(c, vectors, n, dim, m, alpha, seed, graph, times, true, fallback_rows);
+}
+
+// pm_robust_prune: k_prune on given lists, through the build's own second pass
+// (prune_lists); every list by the LDS sort, or every list presorted.
+extern "C" int pm_robust_prune(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* verts,
+                               uint64_t nverts, const uint64_t* offs, const uint32_t* lens, const uint32_t* ids,
+                               uint64_t nids, uint32_t m, float alpha, int presorted, uint32_t* out,
+                               uint32_t* out_len, uint32_t* err) {
+  if (!c || !vectors || !verts || !offs || !lens || (!ids && nids) || !out || !out_len || !err)
+    return fail(PM_EINVAL, "NULL argument");
+  if (m == 0 || m > pmk::prune_max_m()) return fail(PM_EINVAL, "m must be in [1, 64]");
+  if (dim == 0 || dim > pmk::prune_max_dim()) return fail(PM_EINVAL, "dim must be in [1, 256]");
+  if (n == 0 || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be in [1, 2^32-1)");
+  if (nverts == 0 || nverts > n) return fail(PM_EINVAL, "nverts must be in [1, n]");
+  for (uint64_t i = 0; i < nids; ++i)
+    if (ids[i] >= n) return fail(PM_EINVAL, "candidate id out of range");
+  // the kernel addresses lists and results by vertex: one list per vertex
+  std::vector<uint64_t> coff(n + 1, 0);
+  std::vector<uint32_t> clen(n, 0);
+  std::vector<uint8_t> seen(n, 0);
+  for (uint64_t b = 0; b < nverts; ++b) {
+    const uint32_t u = verts[b];
+    if (u >= n) return fail(PM_EINVAL, "vertex out of range");
+    if (seen[u]) return fail(PM_EINVAL, "verts must be distinct");
+    if (offs[b] > nids || lens[b] > nids - offs[b]) return fail(PM_EINVAL, "list outside ids");
+    seen[u] = 1;
+    coff[u] = offs[b];
+    clen[u] = lens[b];
+  }
+  HIPCHK(hipSetDevice(c->device));
+  DevBuf X;
+  CHK(X.reserve(n * dim * 4));
+  HIPCHK(hipMemcpyAsync(X.p, vectors, n * dim * 4, hipMemcpyHostToDevice, c->stream));
+  const std::vector<uint32_t> vs(verts, verts + nverts), none, conn(ids, ids + nids);
+  std::vector<uint32_t> P, PL;
+  CHK(prune_lists(c, X.as<float>(), n, (uint32_t)dim, presorted ? none : vs, presorted ? vs : none, coff, clen, conn, m,
+                  alpha, P, PL, err));
+  for (uint64_t b = 0; b < nverts; ++b) {
+    const uint32_t u = verts[b];
+    out_len[b] = PL[u];
+    memcpy(out + b * m, &P[(uint64_t)u * m], (size_t)std::min<uint32_t>(PL[u], m) * 4);
+  }
+  return 0;
 }

@@ -137,7 +137,8 @@ template <int DP>
 __global__ void __launch_bounds__(kKnnThreads) k_knn_bf16(const __bf16* __restrict__ X, const float* __restrict__ xn,
                                                           uint64_t N, const __bf16* __restrict__ Q,
                                                           const float* __restrict__ qn, uint64_t M,
-                                                          uint32_t* __restrict__ out) {
+                                                          uint32_t* __restrict__ out,
+                                                          uint32_t* __restrict__ out_hi) {
   constexpr int KS = DP / 16;                       // MFMA k-steps
   constexpr int CH = kKnnCols * DP / 8;             // 16-B chunks per tile
   constexpr int PER = CH / kKnnThreads;             // per thread
@@ -238,7 +239,10 @@ __global__ void __launch_bounds__(kKnnThreads) k_knn_bf16(const __bf16* __restri
   }
   for (uint32_t r = w * 8; r < w * 8 + 8; ++r) {
     const uint64_t qr = row0 + r;
-    if (qr < M) out[qr * kKnnTop + lane] = (uint32_t)L.top[r][lane];
+    if (qr < M) {
+      out[qr * kKnnTop + lane] = (uint32_t)L.top[r][lane];
+      if (out_hi) out_hi[qr * kKnnTop + lane] = (uint32_t)(L.top[r][lane] >> 32);
+    }
   }
 }
 
@@ -273,7 +277,8 @@ __global__ void __launch_bounds__(kKnn3Threads) k_knn_bf16x3(const __bf16* __res
                                                              const __bf16* __restrict__ Qh,
                                                              const __bf16* __restrict__ Ql,
                                                              const float* __restrict__ qn, uint64_t M,
-                                                             uint32_t* __restrict__ out, float* __restrict__ tau) {
+                                                             uint32_t* __restrict__ out, float* __restrict__ tau,
+                                                             uint32_t* __restrict__ out_hi) {
   constexpr int KS = DP / 16;
   constexpr int CH = kKnn3Cols * DP / 8;            // 16-B chunks per tile half
   constexpr int PER = CH / kKnn3Threads;
@@ -402,6 +407,7 @@ __global__ void __launch_bounds__(kKnn3Threads) k_knn_bf16x3(const __bf16* __res
     const uint64_t qr = row0 + r;
     if (qr < M) {
       out[qr * kKnnTop + lane] = (uint32_t)L.top[r][lane];
+      if (out_hi) out_hi[qr * kKnnTop + lane] = (uint32_t)(L.top[r][lane] >> 32);
       if (lane == kKnnTop - 1) tau[qr] = __uint_as_float((uint32_t)(L.top[r][lane] >> 32));
     }
   }
@@ -515,7 +521,8 @@ __global__ void __launch_bounds__(kBlock) k_knn_rerank_cert(const float* __restr
                                                             const float* __restrict__ tau,
                                                             const uint32_t* __restrict__ maxnorm, float crel,
                                                             uint64_t* __restrict__ list,
-                                                            unsigned long long* __restrict__ nlist) {
+                                                            unsigned long long* __restrict__ nlist,
+                                                            float* __restrict__ eps_out) {
   __shared__ uint64_t keys[kBlock / 64][64];
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint64_t row = (uint64_t)blockIdx.x * (kBlock / 64) + w;
@@ -527,6 +534,7 @@ __global__ void __launch_bounds__(kBlock) k_knn_rerank_cert(const float* __restr
     const float sum = __fadd_rn(qn[row], __uint_as_float(*maxnorm));
     // rounded up: the factor covers the two roundings of the product and the sum
     const float eps = __fadd_rn(__fmul_rn(__fmul_rn(sum, crel), 1.0f + 0x1.0p-20f), kCertAbs);
+    if (eps_out) eps_out[row] = eps;
     const bool ok = x != kNoKey && sum <= kCertMaxSum && (double)dk < (double)tau[row] - (double)eps;
     if (!ok) list[atomicAdd(nlist, 1ull)] = row;
   }
@@ -657,7 +665,7 @@ __global__ void __launch_bounds__(kBlock) k_prune(const float* __restrict__ X, u
     }
   }   // !pre
   // the greedy pass (:188-212): candidate v is accepted unless an accepted a_j
-  // has L2Dist(a_j, v) * alpha < dist(u, v); all a_j are tested at once
+  // has L2Dist(a_j, v) * alpha < dist(u, v); the a_j are tested 32 at a time
   uint32_t na = 0, nd = 0;
   for (uint32_t s = 0; s < n; ++s) {
     const uint32_t pos = pre ? sorted_pos[off + s] : (uint32_t)L.key[s];
@@ -667,9 +675,9 @@ __global__ void __launch_bounds__(kBlock) k_prune(const float* __restrict__ X, u
     for (uint32_t i = tid; i < dim; i += kBlock) L.acc[na][i] = xv[i];
     __syncthreads();
     bool rej = false;
-    if (g < na) {
-      const float d = l2_group8(L.acc[g], L.acc[na], dim, k);
-      rej = __fmul_rn(d, alpha) < duv;
+    for (uint32_t a = g; a < na; a += kBlock / 8) {   // 32 groups: two rounds once na > 32 (m up to 64)
+      const float d = l2_group8(L.acc[a], L.acc[na], dim, k);
+      rej |= __fmul_rn(d, alpha) < duv;
     }
     const bool any = __syncthreads_or(rej);
     if (!any) {
@@ -724,15 +732,15 @@ void to_bf16(hipStream_t st, const float* rows, uint64_t n, uint32_t dim, uint32
                      norms);
 }
 void knn_prefilter(hipStream_t st, const void* X, const float* xn, uint64_t N, const void* Q, const float* qn,
-                   uint64_t M, uint32_t dp, uint32_t* out) {
+                   uint64_t M, uint32_t dp, uint32_t* out, uint32_t* out_hi) {
   if (!M) return;
   const dim3 grid(gcdiv(M, kKnnRows));
   if (dp == 128)
     hipLaunchKernelGGL(k_knn_bf16<128>, grid, dim3(kKnnThreads), 0, st, (const __bf16*)X, xn, N, (const __bf16*)Q,
-                       qn, M, out);
+                       qn, M, out, out_hi);
   else
     hipLaunchKernelGGL(k_knn_bf16<192>, grid, dim3(kKnnThreads), 0, st, (const __bf16*)X, xn, N, (const __bf16*)Q,
-                       qn, M, out);
+                       qn, M, out, out_hi);
 }
 void knn_rerank(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
                 const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len) {
@@ -747,15 +755,16 @@ void to_bf16x2(hipStream_t st, const float* rows, uint64_t n, uint32_t dim, uint
                      (__bf16*)lo, norms, maxnorm);
 }
 void knn_prefilter_x3(hipStream_t st, const void* Xh, const void* Xl, const float* xn, uint64_t N, const void* Qh,
-                      const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau) {
+                      const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau,
+                      uint32_t* out_hi) {
   if (!M) return;
   const dim3 grid(gcdiv(M, kKnnRows));
   if (dp == 128)
     hipLaunchKernelGGL(k_knn_bf16x3<128>, grid, dim3(kKnn3Threads), 0, st, (const __bf16*)Xh, (const __bf16*)Xl, xn,
-                       N, (const __bf16*)Qh, (const __bf16*)Ql, qn, M, out, tau);
+                       N, (const __bf16*)Qh, (const __bf16*)Ql, qn, M, out, tau, out_hi);
   else
     hipLaunchKernelGGL(k_knn_bf16x3<192>, grid, dim3(kKnn3Threads), 0, st, (const __bf16*)Xh, (const __bf16*)Xl, xn,
-                       N, (const __bf16*)Qh, (const __bf16*)Ql, qn, M, out, tau);
+                       N, (const __bf16*)Qh, (const __bf16*)Ql, qn, M, out, tau, out_hi);
 }
 // the prefilter's 3 dp products summed with at most 2^-23
 // relative error per add, doubled for whatever order and alignment the matrix
@@ -767,11 +776,11 @@ float knn_cert_rel(uint32_t dp) {
 void knn_rerank_cert(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
                      const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len,
                      const float* qn, const float* tau, const uint32_t* maxnorm, uint32_t dp, uint64_t* list,
-                     uint64_t* nlist) {
+                     uint64_t* nlist, float* eps_out) {
   if (!M) return;
   hipLaunchKernelGGL(k_knn_rerank_cert, dim3(gcdiv(M, kBlock / 64)), dim3(kBlock), 0, st, X, N, dim, Q, M, cand, K,
                      (int)self_base, out, dist, len, qn, tau, maxnorm, knn_cert_rel(dp), list,
-                     (unsigned long long*)nlist);
+                     (unsigned long long*)nlist, eps_out);
 }
 void knn_brute(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, const uint64_t* list,
                uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len) {

@@ -477,7 +477,7 @@ uint32_t prune_max_dim();
 uint32_t prune_max_m();
 void to_bf16(hipStream_t st, const float* rows, uint64_t n, uint32_t dim, uint32_t dp, void* out, float* norms);
 void knn_prefilter(hipStream_t st, const void* X, const float* xn, uint64_t N, const void* Q, const float* qn,
-                   uint64_t M, uint32_t dp, uint32_t* out);
+                   uint64_t M, uint32_t dp, uint32_t* out, uint32_t* out_hi = nullptr);
 void knn_rerank(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
                 const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
 // the exact variants (pm_knn_exact): split rows hi + lo with f32 norms and the largest norm's bits,
@@ -487,12 +487,13 @@ void knn_rerank(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const 
 void to_bf16x2(hipStream_t st, const float* rows, uint64_t n, uint32_t dim, uint32_t dp, void* hi, void* lo,
                float* norms, uint32_t* maxnorm);
 void knn_prefilter_x3(hipStream_t st, const void* Xh, const void* Xl, const float* xn, uint64_t N, const void* Qh,
-                      const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau);
+                      const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau,
+                      uint32_t* out_hi = nullptr);
 float knn_cert_rel(uint32_t dp);
 void knn_rerank_cert(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
                      const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len,
                      const float* qn, const float* tau, const uint32_t* maxnorm, uint32_t dp, uint64_t* list,
-                     uint64_t* nlist);
+                     uint64_t* nlist, float* eps_out = nullptr);
 void knn_brute(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, const uint64_t* list,
                uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
 void prune(hipStream_t st, const float* X, uint32_t dim, const uint32_t* verts, uint64_t nverts,

@@ -1,26 +1,17 @@
 """pm_knn_exact and pm_build_graph_exact: the brute-force (L2Dist, id) ranking
 for general float rows, through the certified prefilter or the brute-force
-fallback."""
+fallback, and the shape, order, tie and scale edges of both
+kNN paths end to end.  NaN and infinite inputs are out of contract: they get
+some answer through the fallback, and no test here feeds them."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from tests import knn_ref as R
+from tests.knn_ref import clustered_floats, near_duplicate_rows
+
 pytestmark = pytest.mark.gpu
-
-
-def clustered_floats(n, d, nq=0, centres=20, seed=11):
-    """row i = centre[i % centres] + 0.1 N(0,1); queries = the centres of rows
-    ::80 + 0.1 N(0,1)."""
-    rng = np.random.default_rng(seed)
-    c = rng.standard_normal((centres, d)).astype(np.float32)
-    label = np.arange(n) % centres
-    v = (c[label] + 0.1 * rng.standard_normal((n, d))).astype(np.float32)
-    if not nq:
-        return v
-    ql = label[::80][:nq]
-    q = (c[ql] + 0.1 * rng.standard_normal((len(ql), d))).astype(np.float32)
-    return v, q
 
 
 @pytest.fixture(scope="module")
@@ -70,15 +61,7 @@ def test_forced_fallback_ragged_dim(ctx, oracle):
     the first four queries): no certificate can hold, the brute-force kernel
     answers them, id-order ties included; dim % 8 != 0."""
     import pacmann_amd as pm
-    rng = np.random.default_rng(5)
-    n, d = 300, 100
-    base = rng.standard_normal(d).astype(np.float32)
-    v = rng.standard_normal((n, d)).astype(np.float32)
-    for i in range(100):
-        r = base.copy()
-        r[i % 100] = r[i % 100] + np.float32(i) * np.spacing(r[i % 100])
-        v[i] = r
-    q = np.concatenate([v[[0, 3, 40, 99]], v[[120, 150, 200, 250, 299]] + np.float32(0.5)]).astype(np.float32)
+    v, q = near_duplicate_rows()
     gi, gd, fb = pm.knn_exact(v, q, 20, ctx, with_dist=True)
     oi, od = oracle.knn(v, q, 20)
     assert_equals_oracle(gi, gd, oi, od)
@@ -129,6 +112,115 @@ def test_build_graph_exact_on_floats(ctx, oracle, n, d, m, centres):
     assert (g != np.arange(n, dtype=np.uint32)[:, None]).all()
     assert 0 <= t["knn_fallback_rows"] <= n
     assert t["knn_s"] > 0
+
+
+@pytest.mark.parametrize("n,nq,dim,k,kc", R.shape_cases())
+def test_shape_edges(ctx, oracle, n, nq, dim, k, kc):
+    """n and nq on the tile edges, dim on the chunk and pad edges, k = 1, 64 and
+    one more (above n where n < 63): the oracle's ids and distance bits; beyond
+    n the ids are -1 and the distances +inf."""
+    import pacmann_amd as pm
+    v, q = R.shape_data(n, nq, dim, integer=False)
+    gi, gd, fb = pm.knn_exact(v, q, k, ctx, with_dist=True)
+    oi, od = oracle.knn(v, q, k)
+    assert_equals_oracle(gi, gd, oi, od)
+    if k > n:
+        assert (gi[:, n:] == -1).all() and np.isposinf(gd[:, n:]).all() and (gi[:, :n] >= 0).all()
+    if n <= 64:
+        assert fb == 0
+
+
+@pytest.mark.parametrize("mirror", [False, True])
+def test_descending_order_fills_the_insertion_buffer(ctx, oracle, mirror):
+    """Base rows in descending distance order: every column of every tile goes
+    into the row's insertion buffer (64 per tile, its width).  The mirror
+    ascends: only the first tile inserts."""
+    import pacmann_amd as pm
+    v, q = R.descending_rows(integer=False)
+    if mirror:
+        v = np.ascontiguousarray(v[::-1])
+    q = np.repeat(q, 3, axis=0)
+    for k in (1, 64):
+        gi, gd, _ = pm.knn_exact(v, q, k, ctx, with_dist=True)
+        oi, od = oracle.knn(v, q, k)
+        assert_equals_oracle(gi, gd, oi, od)
+    want = np.arange(64) if mirror else np.arange(1023, 959, -1)
+    assert (gi == want).all()
+
+
+def test_identical_rows_tie_by_id(ctx, oracle):
+    """200 identical rows and queries equal to them: the smallest ids win, and
+    exactly those queries are uncertified (more than 64 rows share the 64th
+    key's distance); a query equal to a lone base row is certified at k = 1."""
+    import pacmann_amd as pm
+    v, q, ntie = R.identical_rows(integer=False)
+    gi, gd, fb = pm.knn_exact(v, q, 1, ctx, with_dist=True)
+    assert_equals_oracle(gi, gd, *oracle.knn(v, q, 1))
+    assert fb == ntie
+    gi, gd, fb = pm.knn_exact(v, q, 64, ctx, with_dist=True)
+    assert_equals_oracle(gi, gd, *oracle.knn(v, q, 64))
+    assert (gi[:ntie] == np.arange(10, 74)).all() and (gd[:ntie] == 0).all()
+    assert fb >= ntie
+
+
+def test_equidistant_rows_tie_by_id(ctx, oracle):
+    """200 rows at one exact non-zero L2Dist, in the first and the last tiles:
+    the prefilter's own distances of them differ, the certificate must refuse
+    the rows, and the smallest ids win."""
+    import pacmann_amd as pm
+    v, q, ntie = R.equidistant_rows(integer=False)
+    for k in (1, 64):
+        gi, gd, fb = pm.knn_exact(v, q, k, ctx, with_dist=True)
+        assert_equals_oracle(gi, gd, *oracle.knn(v, q, k))
+        assert fb == ntie == len(q)
+    assert (gi == np.arange(64)).all() and (gd == np.float32(0.25)).all()
+
+
+@pytest.mark.parametrize("exp", [-70, -25, 30, 58])
+def test_scaled_rows(ctx, oracle, exp):
+    """The clustered rows times a power of two: ids and distance bits of the
+    oracle (2^-70: the distances are f32 subnormals and the 2^-50 term is the
+    whole eps, so every row is uncertified; 2^58: the sums stay below 2^126)."""
+    import pacmann_amd as pm
+    v, q = clustered_floats(1000, 100, nq=50)
+    s = np.float32(2.0) ** np.float32(exp)
+    v, q = v * s, q * s
+    oi, od = oracle.knn(v, q, 10)
+    assert np.isfinite(od).all()
+    if exp == -70:
+        assert (od < 2.0 ** -126).all() and (od > 0).all()
+    gi, gd, fb = pm.knn_exact(v, q, 10, ctx, with_dist=True)
+    print(f"scale 2^{exp}: fallback_rows {fb} of {len(q)}")
+    assert_equals_oracle(gi, gd, oi, od)
+    if exp == -70:
+        assert fb == len(q)
+
+
+def test_one_huge_row_uncertifies_all(ctx, oracle):
+    """One base row of norm about 2^100 among unit rows: eps follows the largest
+    norm, far above every distance, so every row goes to the fallback."""
+    import pacmann_amd as pm
+    v, q = clustered_floats(1000, 100, nq=50)
+    v[500] = v[500] * np.float32(2.0 ** 47)   # |x|^2 about 100 * 2^94
+    assert 2.0 ** 99 < R.norms64(v[500:501])[0] < 2.0 ** 102
+    gi, gd, fb = pm.knn_exact(v, q, 10, ctx, with_dist=True)
+    assert_equals_oracle(gi, gd, *oracle.knn(v, q, 10))
+    assert fb == len(q)
+
+
+def test_overflowing_norms_uncertify_all(ctx, oracle):
+    """Scale 2^62: the norms overflow, sum <= 2^126 fails for every row; the
+    oracle's +inf distances are ranked by id."""
+    import pacmann_amd as pm
+    v, q = clustered_floats(1000, 100, nq=50)
+    s = np.float32(2.0 ** 62)
+    v, q = v * s, q * s
+    assert np.isfinite(v).all() and np.isfinite(q).all() and R.norms64(v).min() > R.MAX_SUM
+    oi, od = oracle.knn(v, q, 64)   # 50 rows per cluster at finite distances, then +inf by id
+    assert np.isposinf(od[:, 50:]).all() and np.isfinite(od[:, :40]).all()
+    gi, gd, fb = pm.knn_exact(v, q, 64, ctx, with_dist=True)
+    assert_equals_oracle(gi, gd, oi, od)
+    assert fb == len(q)
 
 
 def test_argument_checks(ctx):

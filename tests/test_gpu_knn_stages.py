@@ -1,0 +1,166 @@
+"""The stages of pm_knn_exact against the plain reference (tests/knn_ref.py),
+through pm_knn_stages: the bf16 split and the norms bit for bit, the measured
+error of the three-product prefilter against the bound eps the certificate
+relies on, and the certificate's premise on data with more
+than 64 base rows.  NaN and infinite inputs are out of contract: no case."""
+import numpy as np
+import pytest
+
+from tests import knn_ref as R
+
+pytestmark = pytest.mark.gpu
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("dim", [1, 63, 64, 65, 128, 129, 192])
+def test_split_and_norms_bit_for_bit(ctx, dim):
+    """hi, lo, the padding, the norms in the kernel's fixed order and the bits of
+    the largest norm, on every value family; as base rows and as query rows."""
+    import pacmann_amd as pm
+    rows = R.split_rows_mixed(dim)
+    n = len(rows)
+    assert n <= 64
+    s = pm.knn_stages(rows, rows, 1, ctx)
+    hi, lo = R.split_rows(rows)
+    assert s["dp"] == R.pad_dim(dim) and s["bhi"].shape == hi.shape
+    fam = np.repeat(np.array(R.SPLIT_FAMILIES), n // len(R.SPLIT_FAMILIES))
+    for name, got, want in (("hi", s["bhi"], hi), ("lo", s["blo"], lo)):
+        bad = np.argwhere(got != want)
+        assert not len(bad), (name, fam[bad[0][0]], bad[0].tolist(), hex(got[tuple(bad[0])]), hex(want[tuple(bad[0])]),
+                              hex(int(bits(rows)[bad[0][0], min(bad[0][1], dim - 1)])))
+    norms = R.norms_fixed_order(rows)
+    for name in ("bnorm", "qnorm"):
+        bad = np.flatnonzero(bits(s[name]) != bits(norms))
+        assert not len(bad), (name, fam[bad[0]], float(s[name][bad[0]]), float(norms[bad[0]]))
+    assert s["maxnorm"] == int(bits(norms).max())
+    assert (norms[fam == "subnormal"] == 0).all()   # squares of f32 subnormals vanish in the reference too
+
+
+def pref_by_id(s, n):
+    """The probe's prefilter distances as [nq][n] by base id (n <= 64: every base
+    row is a candidate, once)."""
+    cand, pref = s["cand"], s["pref"]
+    assert (np.sort(cand[:, :n], axis=1) == np.arange(n, dtype=np.uint32)).all()
+    assert (cand[:, n:] == R.EMPTY).all() and (bits(pref[:, n:]) == R.EMPTY).all()
+    out = np.empty((len(cand), n), np.float32)
+    np.put_along_axis(out, cand[:, :n].astype(np.int64), pref[:, :n], axis=1)
+    return out
+
+
+@pytest.mark.parametrize("dim", R.PREF_DIMS)
+@pytest.mark.parametrize("family", R.PREF_FAMILIES)
+def test_prefilter_error_within_eps(ctx, oracle, family, dim):
+    """|prefilter distance - L2Dist| <= c_dp (|q|^2 + |x|^2) + 2^-50 for every
+    (q, x) pair, against the oracle's L2Dist and against the float64 distance:
+    the bound the certificate's proof derives.  Prints the largest error / bound."""
+    import pacmann_amd as pm
+    q, x = R.pref_family(family, dim)
+    dp = R.pad_dim(dim)
+    s = pm.knn_stages(x, q, 1, ctx)
+    pref = pref_by_id(s, len(x)).astype(np.float64)
+    assert np.isfinite(pref).all() and (pref >= 0).all()
+    bound = R.eps_bound(dp, R.norms64(q)[:, None], R.norms64(x)[None, :])
+    d_or = R.oracle_dist(oracle, q, x)
+    r_or = np.abs(pref - d_or.astype(np.float64)) / bound
+    r_64 = np.abs(pref - R.dist64(q, x)) / bound
+    i, j = np.unravel_index(np.argmax(r_or), r_or.shape)
+    print(f"PREFILTER_SLACK dp={dp} dim={dim} family={family} max_err_over_bound oracle={r_or.max():.4f} "
+          f"float64={r_64.max():.4f} (pair q{i} x{j}: pref {pref[i, j]!r} L2Dist {float(d_or[i, j])!r} bound {bound[i, j]!r})")
+    assert r_or.max() <= 1.0, (i, j)
+    assert r_64.max() <= 1.0
+    if family == "integer":   # every product and partial sum is an exact integer: no error at all
+        assert np.array_equal(bits(pref.astype(np.float32)), bits(d_or))
+        s1 = pm.knn_stages(x, q, 1, ctx, exact=False)
+        assert np.array_equal(bits(pref_by_id(s1, len(x))), bits(d_or))
+
+
+def premise_data(name):
+    if name == "near_duplicates":
+        return R.near_duplicate_rows()
+    return R.clustered_floats(1000, int(name[1:]), nq=50)
+
+
+@pytest.fixture(scope="module", params=["d100", "d192", "near_duplicates"])
+def premise(request, oracle):
+    v, q = premise_data(request.param)
+    od_all = R.oracle_dist(oracle, q, v)
+    oi, od = oracle.knn(v, q, 64)
+    return v, q, od_all, oi, od
+
+
+def test_certificate_premise(ctx, premise):
+    """n > 64: the keys are strictly ascending, tau is the 64th prefilter
+    distance, no base row outside the 64 lies more than the row's eps below tau,
+    and that eps is at least the derived bound."""
+    import pacmann_amd as pm
+    v, q, od_all, _, _ = premise
+    s = pm.knn_stages(v, q, 10, ctx)
+    cand, pref = s["cand"], s["pref"]
+    assert (cand < len(v)).all() and (pref >= 0).all()
+    keys = (bits(pref).astype(np.uint64) << np.uint64(32)) | cand
+    assert (keys[:, 1:] > keys[:, :-1]).all()
+    assert np.array_equal(bits(s["tau"]), bits(pref[:, 63]))
+    tau, eps = s["tau"].astype(np.float64), s["eps"].astype(np.float64)
+    assert np.isfinite(eps).all()
+    qn, xn = R.norms64(q), R.norms64(v)
+    assert (eps >= R.eps_bound(s["dp"], qn, xn.max())).all()
+    assert s["maxnorm"] == int(bits(s["bnorm"]).max())
+    slack = []
+    for r in range(len(q)):
+        outside = np.ones(len(v), bool)
+        outside[cand[r]] = False
+        assert outside.sum() == len(v) - 64
+        d = od_all[r, outside].astype(np.float64)
+        assert (d >= tau[r] - eps[r]).all(), (r, d.min(), tau[r], eps[r])
+        slack.append((tau[r] - d.min()) / eps[r])
+        # each candidate's prefilter distance is within eps of its L2Dist as well
+        assert (np.abs(pref[r].astype(np.float64) - od_all[r, cand[r]]) <= eps[r]).all()
+    print(f"PREMISE n={len(v)} dim={v.shape[1]}: max (tau - nearest outside) / eps = {max(slack):.4f}")
+
+
+@pytest.mark.parametrize("k", [1, 10, 48, 64])
+def test_uncertified_rows(ctx, premise, k):
+    """The uncertified list is exactly the rows for which dK < tau - eps fails in
+    float64, its length is pm_knn_exact's fallback_rows, and the results are
+    the oracle's either way."""
+    import pacmann_amd as pm
+    v, q, _, oi, od = premise
+    s = pm.knn_stages(v, q, k, ctx)
+    dk = od[:, k - 1].astype(np.float64)
+    fails = ~(dk < s["tau"].astype(np.float64) - s["eps"].astype(np.float64))
+    assert s["uncertified"].tolist() == np.flatnonzero(fails).tolist()
+    gi, gd, fb = pm.knn_exact(v, q, k, ctx, with_dist=True)
+    assert fb == len(s["uncertified"])
+    assert np.array_equal(gi, oi[:, :k]) and np.array_equal(bits(gd), bits(od[:, :k]))
+    print(f"UNCERTIFIED n={len(v)} dim={v.shape[1]} k={k}: {fb} of {len(q)}")
+
+
+def test_argument_checks(ctx):
+    """PM_EINVAL with a text, before any HIP call."""
+    import ctypes as C
+
+    import pacmann_amd as pm
+    L = pm.lib()
+    v = np.zeros((64, 193), dtype=np.float32)
+    cand, pref = np.zeros((1, 64), np.uint32), np.zeros((1, 64), np.float32)
+    o = pm.KnnStagesOut()
+    o.cand, o.pref = cand.ctypes.data_as(pm.u32p), pref.ctypes.data_as(pm.f32p)
+    empty = pm.KnnStagesOut()
+    vp = v.ctypes.data_as(pm.f32p)
+    cases = [
+        (lambda: L.pm_knn_stages(None, vp, 64, 16, vp, 1, 10, 1, C.byref(o)), b"NULL argument"),
+        (lambda: L.pm_knn_stages(ctx.h, vp, 64, 16, vp, 1, 10, 1, None), b"NULL argument"),
+        (lambda: L.pm_knn_stages(ctx.h, vp, 64, 16, vp, 1, 10, 1, C.byref(empty)), b"NULL argument"),
+        (lambda: L.pm_knn_stages(ctx.h, vp, 64, 16, vp, 1, 0, 1, C.byref(o)), b"k must be in [1, 64]"),
+        (lambda: L.pm_knn_stages(ctx.h, vp, 64, 16, vp, 1, 65, 0, C.byref(o)), b"k must be in [1, 64]"),
+        (lambda: L.pm_knn_stages(ctx.h, vp, 0, 16, vp, 1, 10, 1, C.byref(o)), b"n must be in [1, 2^32-1)"),
+        (lambda: L.pm_knn_stages(ctx.h, vp, 64, 16, vp, 0, 10, 1, C.byref(o)), b"nq must be > 0"),
+        (lambda: L.pm_knn_stages(ctx.h, vp, 64, 193, vp, 1, 10, 0, C.byref(o)), b"kNN supports dim <= 192"),
+    ]
+    for call, want in cases:
+        assert L.pm_ctx_mem_info(None, None, None) == -1   # another text first
+        assert call() == -1
+        assert L.pm_last_error().startswith(want), L.pm_last_error()

@@ -802,6 +802,61 @@ def test_knn_exact_integer_rows(ctx, oracle, n, dim):
     assert np.array_equal(gd.view(np.uint32), od.view(np.uint32))
 
 
+def _knn_equals_oracle(ctx, oracle, v, q, k):
+    import pacmann_amd as pm
+    gi, gd = pm.knn(v, q, k, ctx, with_dist=True)
+    oi, od = oracle.knn(v, q, k)
+    assert np.array_equal(gi, oi)
+    assert np.array_equal(gd.view(np.uint32), od.view(np.uint32))
+    return gi, gd
+
+
+def _shape_cases():
+    from tests.knn_ref import shape_cases
+    return shape_cases()
+
+
+@pytest.mark.parametrize("n,nq,dim,k,kc", _shape_cases())
+def test_knn_integer_shape_edges(ctx, oracle, n, nq, dim, k, kc):
+    """pm_knn on integer rows with n and nq on the tile edges (128 columns, 64
+    rows), dim on the k-step and pad edges, k = 1, 64 and one more (above n
+    where n < 63, padded with -1 / +inf)."""
+    from tests.knn_ref import shape_data
+    v, q = shape_data(n, nq, dim, integer=True)
+    gi, gd = _knn_equals_oracle(ctx, oracle, v, q, k)
+    if k > n:
+        assert (gi[:, n:] == -1).all() and np.isposinf(gd[:, n:]).all() and (gi[:, :n] >= 0).all()
+
+
+@pytest.mark.parametrize("mirror", [False, True])
+def test_knn_integer_descending_order(ctx, oracle, mirror):
+    """Base rows in descending distance order: all 128 columns of every tile go
+    into the row's insertion buffer, its width; the mirror ascends."""
+    from tests.knn_ref import descending_rows
+    v, q = descending_rows(integer=True)
+    if mirror:
+        v = np.ascontiguousarray(v[::-1])
+    q = np.repeat(q, 3, axis=0)
+    _knn_equals_oracle(ctx, oracle, v, q, 1)
+    gi, gd = _knn_equals_oracle(ctx, oracle, v, q, 64)
+    assert (gi == (np.arange(64) if mirror else np.arange(1023, 959, -1))).all()
+    assert (gd == np.arange(1, 65, dtype=np.float32)).all()
+
+
+def test_knn_integer_ties_beyond_64(ctx, oracle):
+    """More than 64 exact ties at the 64th key (200 identical rows; 200 rows at
+    one non-zero distance in the first and last tiles): the smallest ids win."""
+    from tests.knn_ref import equidistant_rows, identical_rows
+    v, q, ntie = identical_rows(integer=True)
+    _knn_equals_oracle(ctx, oracle, v, q, 1)
+    gi, gd = _knn_equals_oracle(ctx, oracle, v, q, 64)
+    assert (gi[:ntie] == np.arange(10, 74)).all() and (gd[:ntie] == 0).all()
+    v, q, ntie = equidistant_rows(integer=True)
+    _knn_equals_oracle(ctx, oracle, v, q, 1)
+    gi, gd = _knn_equals_oracle(ctx, oracle, v, q, 64)
+    assert (gi == np.arange(64)).all() and (gd == 1).all()
+
+
 def test_knn_float_rows_overlap(ctx, oracle):
     """General float rows: the bf16 prefilter keeps 64 candidates for the exact
     re-rank of the top 10; the result matches brute force on >= 99% of ids,
