@@ -101,6 +101,14 @@ int pm_timing_enable(pm_ctx* ctx, int level);
  * the form it was created with for all its preprocessings, a client of a server
  * without an image goes without one, and clients preprocessed as one group
  * must agree (PM_EINVAL otherwise).
+ * "fold_pack": whether a graph DB (pm_graph_*) whose coordinates all have zero
+ * low halves (f32 holding small integers, e.g. SIFT's bytes; detected once,
+ * when the server packs its DB) gets a packed fold image without those halves
+ * (1, at ChunkSize 512 and dim % 16 == 0) or the plain image (0); -1:
+ * PM_FOLD_PACK (default on); any other value is PM_EINVAL.  Read when a server
+ * is created; its clients and sessions share the image and the decision.
+ * "host_fold_rot512p" counts the folds over a packed image, "host_fold_rot512"
+ * those over a plain one.
  * "device_loop": the batched serving loop on the device (1 / 0; -1 automatic).
  * "fault_drl_query" (tests): the device loop fails before queueing query
  * `value` (-1 off); its sessions are then unusable (every later call on them
@@ -134,6 +142,18 @@ typedef struct pm_step_forms {
   uint32_t nhelp, nsplit, qw, np_live, cblk, no_guess, qset, args_valid;
 } pm_step_forms;
 int pm_step_plan(const pm_step_shape* shape, pm_step_forms* out);
+/* The index map of the fold image the server builds (k_fold_image), as the
+ * kernel itself evaluates it.  Host arithmetic only.  A partition of ChunkSize
+ * cs (512 / 1,024) and SetSize ss with E-word entries has an image of *nitems
+ * 16-B items; for items [x0, x0 + n): row[i] the partition row the item is
+ * taken from (rows past the partition's end are stored as zero), word[i] the
+ * first 32-bit word of that row it holds, is_packed[i] 0 if it holds four whole
+ * words, 1 if it holds the high halves of eight as consecutive half-words.
+ * packed != 0: the packed image of entries whose first dim 32-bit words are
+ * coordinates, *npk its packed slices; PM_EINVAL if such entries have none
+ * (dim % 16 != 0, coordinates beyond the folded words, cs != 512). */
+int pm_fold_image_map(uint32_t cs, uint32_t ss, uint32_t E, uint32_t dim, int packed, uint64_t x0, uint64_t n,
+                      uint64_t* row, uint32_t* word, uint8_t* is_packed, uint64_t* nitems, uint32_t* npk);
 int pm_timing_reset(pm_ctx* ctx);
 /* Diagnostics: append one line "kernel,start_us,end_us,ctx" per timed launch
  * of ctx (level >= 2 timing) to the file at `path`, on one time axis for every

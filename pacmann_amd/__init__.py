@@ -92,6 +92,8 @@ SIGNATURES = {
     "pm_timing_enable": (C.c_int, [vp, C.c_int]),
     "pm_set_option": (C.c_int, [C.c_char_p, C.c_int]),
     "pm_step_plan": (C.c_int, [C.POINTER(StepShape), C.POINTER(StepForms)]),
+    "pm_fold_image_map": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u64, u64, u64p, u32p, u8p,
+                                    u64p, u32p]),
     "pm_timing_reset": (C.c_int, [vp]),
     "pm_timing_get": (C.c_int, [vp, C.c_char_p, u64p, C.POINTER(dbl), C.POINTER(dbl)]),
     "pm_timing_timeline": (C.c_int, [vp, C.c_char_p]),
@@ -306,8 +308,23 @@ def prf_batch(rk: np.ndarray, tags, xs, ctx: Context | None = None) -> np.ndarra
 def set_option(name: str, value: int) -> None:
     """pm_set_option: choose among equivalent kernel paths process-wide
     ("match_part", "match_part8", "match_resolve"; -2 restores the default;
-    "aes_bs" and "fold_rot" 1 / 0, -1 restores the default)."""
+    "aes_bs", "fold_rot" and "fold_pack" 1 / 0, -1 restores the default)."""
     _check(lib().pm_set_option(name.encode(), int(value)))
+
+
+def fold_image_map(cs: int, ss: int, E: int, dim: int = 0, packed: bool = False, x0: int = 0, n: int | None = None):
+    """pm_fold_image_map: where the 16-B items [x0, x0 + n) (default: all) of a partition's fold image come
+    from (no GPU needed).  Returns (row [n] uint64, word [n] uint32, is_packed [n] bool, nitems, npk)."""
+    nitems, npk = C.c_uint64(), C.c_uint32()
+    if n is None:
+        e = np.zeros(0, dtype=np.uint64)
+        _check(lib().pm_fold_image_map(cs, ss, E, dim, int(packed), 0, 0, _p(e, u64p), None, None,
+                                       C.byref(nitems), C.byref(npk)))
+        n = nitems.value - x0
+    row, word, pk = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+    _check(lib().pm_fold_image_map(cs, ss, E, dim, int(packed), x0, n, _p(row, u64p), _p(word, u32p), _p(pk, u8p),
+                                   C.byref(nitems), C.byref(npk)))
+    return row, word, pk.astype(bool), nitems.value, npk.value
 
 
 def step_plan(kind: int, np_: int, nsub: int, max_per_part: int, maxPH: int, maxSS: int, E: int, *,

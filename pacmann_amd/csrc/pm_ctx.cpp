@@ -151,6 +151,11 @@ extern "C" int pm_set_option(const char* name, int value) {
     pmk::set_fold_rot(value);
     return 0;
   }
+  if (!strcmp(name, "fold_pack")) {
+    if (value < -1 || value > 1) return fail(PM_EINVAL, "fold_pack takes 1, 0 or -1");
+    pmk::set_fold_pack(value);
+    return 0;
+  }
   if (pmk::set_option(name, value)) return fail(PM_EINVAL, std::string("unknown option ") + name);
   return 0;
 }
@@ -176,6 +181,20 @@ extern "C" int pm_step_plan(const pm_step_shape* in, pm_step_forms* out) {
   }
   out->nhelp = p.nhelp; out->nsplit = p.nsplit; out->qw = p.qw; out->np_live = p.np_live; out->cblk = p.cblk;
   out->no_guess = p.no_guess; out->qset = p.qset; out->args_valid = s.args_valid;
+  return 0;
+}
+// pmk::fold_image_map, the map k_fold_image itself evaluates.  Host arithmetic only.
+extern "C" int pm_fold_image_map(uint32_t cs, uint32_t ss, uint32_t E, uint32_t dim, int packed, uint64_t x0,
+                                 uint64_t n, uint64_t* row, uint32_t* word, uint8_t* is_packed, uint64_t* nitems,
+                                 uint32_t* npk_out) {
+  if ((n && (!row || !word || !is_packed)) || !nitems || !npk_out) return fail(PM_EINVAL, "NULL argument");
+  if ((cs != 512 && cs != 1024) || ss == 0 || ss % 4 || E < 4 || E % 2) return fail(PM_EINVAL, "not a fold image shape");
+  const uint32_t npk = packed ? pmk::fold_pack_shape(E, dim) : 0;
+  if (packed && (!npk || cs != 512)) return fail(PM_EINVAL, "these entries have no packed fold image");
+  *nitems = pmk::fold_image_words(ss, E, cs, npk) / 2;
+  *npk_out = npk;
+  if (x0 > *nitems || n > *nitems - x0) return fail(PM_EINVAL, "items past the image");
+  pmk::fold_image_map(cs, ss, npk, x0, n, row, word, is_packed);
   return 0;
 }
 extern "C" int pm_timing_reset(pm_ctx* c) {

@@ -53,7 +53,7 @@ namespace pmh {
 int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t B,
                          const uint64_t* rawDB, uint64_t F, uint64_t seed, bool batch,
                          uint32_t shard, uint32_t nshards, const Engine* server,
-                         const DbGen* gen) {
+                         const DbGen* gen, uint32_t coord_words) {
   if (nshards == 0 || shard >= nshards) return fail(PM_EINVAL, "shard must be < nshards");
   if (!ctx) return fail(PM_EINVAL, "ctx is NULL");
   if (!rawDB && N && !server && !gen) return fail(PM_EINVAL, "rawDB is NULL");
@@ -141,12 +141,26 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
   // the device memory still free, or for a client of a server without one.
   // The option is read here and nowhere later: off_img decides the table
   // allocation below and the fold form of every preprocessing of this engine.
+  // A graph DB (coord_words: the 32-bit coordinate words that begin every
+  // entry; 0 for a bare PIR engine, which never qualifies) whose coordinates
+  // all have zero low halves, e.g. f32 holding SIFT's bytes, gets the packed
+  // image (FOLD_ROT512P): one reduction over the rows decides, once, since the
+  // DB does not change.  A client takes its server's image and decision.
   uint64_t off_img = 0;
   if (!g->owned_list.empty() && pmk::fold_image_ok(g->minCS, g->maxCS, (uint32_t)g->E)) {
+    if (server) {
+      g->img_npk = server->img_npk;
+    } else if (const uint32_t npk = pmk::fold_pack_slices(g->minCS, g->maxCS, (uint32_t)g->E, coord_words)) {
+      DevBuf flag;
+      CHK(flag.reserve(64));
+      if (pmk::coord_low_zero(ctx->stream, g->db->as<uint64_t>(), off_db, (uint32_t)g->E, coord_words, flag.as<uint32_t>()))
+        g->img_npk = npk;
+      HIPCHK(hipGetLastError());
+    }
     for (uint32_t i : g->owned_list) {
       PmPart& d = g->parts[i].d;
       d.img = (const uint64_t*)(uintptr_t)off_img;
-      off_img += pmk::fold_image_words(d.SS, (uint32_t)g->E, (uint32_t)g->maxCS);
+      off_img += pmk::fold_image_words(d.SS, (uint32_t)g->E, (uint32_t)g->maxCS, g->img_npk);
     }
     size_t free_b = 0, total_b = 0;
     if (!server && hipMemGetInfo(&free_b, &total_b) == hipSuccess && off_img * 8 > free_b / 4) {
@@ -156,6 +170,7 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
       for (uint32_t i : g->owned_list) g->parts[i].d.img = nullptr;
       off_img = 0;
     }
+    if (!off_img) g->img_npk = 0;
   }
   if (off_img) {
     if (server) {
@@ -165,7 +180,7 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
       for (uint32_t i : g->owned_list) {
         const PmPart& d = g->parts[i].d;
         pmk::fold_image(ctx->stream, g->img->as<uint64_t>() + (uintptr_t)d.img, g->db->as<uint64_t>() + d.row0 * g->E,
-                        d.N, d.SS, (uint32_t)g->E, (uint32_t)g->maxCS);
+                        d.N, d.SS, (uint32_t)g->E, (uint32_t)g->maxCS, g->img_npk);
       }
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -364,9 +379,10 @@ int engine_prep_launch(pm_ctx* c, const Engine* g, const PmPart* dp, int np, con
     // server's); with the shape it fixes the fold form for the engine's lifetime
     int kind = pmk::FOLD_GATHER;
     c->timed("prep_fold", fold, [&] { kind = pmk::prep_fold(st, dp, np, g->maxH, g->db->as<uint64_t>(), (uint32_t)g->E, g->minCS,
-                                                      g->maxCS, g->zero16.as<uint64_t>(), clients, g->img->p != nullptr, minH); });
-    if (kind == pmk::FOLD_ROT512 || kind == pmk::FOLD_ROT1024) {
-      c->host_add(kind == pmk::FOLD_ROT512 ? HT_FOLD_ROT512 : HT_FOLD_ROT1024, 0.0);
+                                                      g->maxCS, g->zero16.as<uint64_t>(), clients, g->img->p != nullptr, minH,
+                                                      g->img_npk); });
+    if (kind == pmk::FOLD_ROT512 || kind == pmk::FOLD_ROT512P || kind == pmk::FOLD_ROT1024) {
+      c->host_add(kind == pmk::FOLD_ROT512 ? HT_FOLD_ROT512 : kind == pmk::FOLD_ROT512P ? HT_FOLD_ROT512P : HT_FOLD_ROT1024, 0.0);
     } else {
       c->host_add(HT_FOLD_OTHER, 0.0);
       c->host_add(kind == pmk::FOLD_PIPE ? HT_FOLD_PIPE : kind == pmk::FOLD_BLK ? HT_FOLD_BLK : HT_FOLD_GATHER, 0.0);

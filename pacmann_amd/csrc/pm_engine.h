@@ -24,7 +24,7 @@ namespace pmh {
 int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t B,
                   const uint64_t* rawDB, uint64_t F, uint64_t seed, bool batch,
                   uint32_t shard = 0, uint32_t nshards = 1, const Engine* server = nullptr,
-                  const DbGen* gen = nullptr);
+                  const DbGen* gen = nullptr, uint32_t coord_words = 0);
 int ensure_host_cache(Engine* g);
 int engine_prep_host(Engine* g, uint64_t p0, uint64_t p1, std::vector<uint64_t>& todo,
                      hipStream_t st = nullptr);
@@ -218,6 +218,7 @@ struct Engine {
 
   std::shared_ptr<DevBuf> db = std::make_shared<DevBuf>();   // server DB; shared by the clients of pm_batchpir_create_client
   std::shared_ptr<DevBuf> img = std::make_shared<DevBuf>();  // the DB's fold image (pmk::fold_image), shared likewise
+  uint32_t img_npk = 0;   // its packed coordinate slices (FOLD_ROT512P; 0: a plain image), the server's for a client
   DevBuf zero16, parts_d, owned_d, tag, pp, parity, ridx, rval, hist, fqn, arena, tab, tabT, cur, done, gran;
   HostBuf parts_stage;   // pinned copy of [parts | owned parts] for the asynchronous upload (upload_parts_async)
   hipEvent_t stage_ev = nullptr;   // the last upload from parts_stage (the stage is rewritten only after it)

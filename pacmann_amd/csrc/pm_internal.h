@@ -112,7 +112,8 @@ struct PmPart {
   // where k_prep_fold_rot does not apply): per 32-B column slice s and group
   // of NCH chunks b (4 at CS 512, 2 at CS 1,024), the 64 KB LDS image
   // k_prep_fold_rot stages, line k = row k of chunks NCH b .. (rows past N
-  // zero).  pmk::fold_image_words.
+  // zero).  pmk::fold_image_words.  Packed (FOLD_ROT512P): the coordinate
+  // slices hold high halves only, 16 words per slice (k_fold_image).
   const PM_G uint64_t* img;
 };
 
@@ -122,6 +123,8 @@ struct PmPart {
 __host__ __device__ inline uint64_t tabT_index(uint32_t H, uint32_t t, uint32_t c) {
   return ((uint64_t)(c >> 3) * H + t) * 8 + (c & 7);
 }
+// where a 16-B item of a fold image comes from (k_fold_image, fold_image_src)
+struct FoldImageSrc { uint64_t row; uint32_t word; bool packed; };
 __host__ __device__ inline uint64_t tabT_words(uint32_t H, uint32_t SS) { return (uint64_t)((SS + 7) / 8) * 8 * H; }
 
 // Hint-search table layout: [SS / 2][PH8 / 8][2][8] u16 (PH8 = PH rounded up
@@ -332,18 +335,22 @@ void set_aes_bs(int v);
 // chunks too wide for LDS), the bank-rotated k_prep_fold_rot<512 / 1024> over
 // the fold image, the pipelined k_prep_fold_pipe (one ChunkSize of 512, 1,024
 // or 2,048 and no image) and the double-buffered k_prep_fold_blk<8 / 4 / 2>.
-enum : int { FOLD_GATHER = 0, FOLD_ROT512 = 1, FOLD_ROT1024 = 2, FOLD_PIPE = 3, FOLD_BLK = 4 };
+// FOLD_ROT512P is k_prep_fold_rot<512> over a packed image: the DB is a graph
+// DB whose coordinate words (f32 holding small integers, e.g. SIFT's bytes) all
+// have zero low halves, so the image and the fold leave those halves out.
+enum : int { FOLD_GATHER = 0, FOLD_ROT512 = 1, FOLD_ROT1024 = 2, FOLD_PIPE = 3, FOLD_BLK = 4, FOLD_ROT512P = 5 };
 // The one selection of the form: from the partitions' ChunkSize range, the entry
-// words and whether the engine was created with a fold image.  prep_fold
-// dispatches on it and fold_needs_tab follows from it.
-int fold_form(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img);
+// words, whether the engine was created with a fold image and the image's packed
+// coordinate slices (npk, 0: a plain image).  prep_fold dispatches on it and
+// fold_needs_tab follows from it.
+int fold_form(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img, uint32_t npk = 0);
 // "fold_rot": 1 / 0 the rotated fold and its image for engines created from now
 // on, -1 = PM_FOLD_ROT's value (default on).  Consulted by fold_image_ok only,
 // i.e. when an engine is created; an existing engine keeps its form.
 void set_fold_rot(int v);
 int prep_fold(hipStream_t st, const PmPart* dparts, int nparts, uint32_t maxH, const uint64_t* db,
               uint32_t E, uint32_t minCS, uint32_t maxCS, const uint64_t* zero16, uint32_t clients = 1,
-              bool have_img = false, uint32_t minH = 0);
+              bool have_img = false, uint32_t minH = 0, uint32_t npk = 0);
 void prep_repl(hipStream_t st, const PmPart* dparts, int nparts, uint32_t maxRepl,
                const uint64_t* db, uint32_t E);
 // The bank-rotated fold's DB image (CS 512 / 1,024, even E, E >= 4): whether an
@@ -354,9 +361,26 @@ bool fold_image_ok(uint32_t minCS, uint32_t maxCS, uint32_t E);
 // whether the fold of these shapes reads the chunk-major PRF table PmPart::tab
 // (otherwise it is not allocated: every other reader uses tabT)
 bool fold_needs_tab(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img);
-uint64_t fold_image_words(uint32_t SS, uint32_t E, uint32_t CS);
+uint64_t fold_image_words(uint32_t SS, uint32_t E, uint32_t CS, uint32_t npk = 0);
 void fold_image(hipStream_t st, uint64_t* img, const uint64_t* part_rows, uint64_t N, uint32_t SS, uint32_t E,
-                uint32_t CS);
+                uint32_t CS, uint32_t npk = 0);
+// The packed image.  fold_pack_shape: the packed coordinate slices of entries of
+// E words whose first `dim` 32-bit words are coordinates (16 per slice), 0 where
+// they do not fill whole slices of the folded words.  fold_pack_slices: the same
+// for an engine being created, 0 also unless its fold is FOLD_ROT512 and
+// "fold_pack" / PM_FOLD_PACK (1 / 0, -1 the environment's, default on) allows
+// it.  coord_low_zero: one reduction over the packed DB rows, true if the low
+// half of every coordinate word of every row is zero (flag: 4 device bytes;
+// false on a HIP error too).  Both are asked once, when a server packs its DB.
+void set_fold_pack(int v);
+uint32_t fold_pack_shape(uint32_t E, uint32_t dim);
+uint32_t fold_pack_slices(uint32_t minCS, uint32_t maxCS, uint32_t E, uint32_t dim);
+bool coord_low_zero(hipStream_t st, const uint64_t* rows, uint64_t nrows, uint32_t E, uint32_t dim, uint32_t* flag);
+// k_fold_image's index map on the host (pm_fold_image_map): for image items
+// [x0, x0 + n) of a partition, the row, its first 32-bit word and whether the
+// item packs the high halves of 8 words (else it holds 4 whole words)
+void fold_image_map(uint32_t CS, uint32_t SS, uint32_t npk, uint64_t x0, uint64_t n, uint64_t* row, uint32_t* word,
+                    uint8_t* packed);
 // Timing events carried by a launch's own dispatch packet (null: untimed)
 struct PmEvents { hipEvent_t a = nullptr, b = nullptr; };
 // pm_set_option: the hint-search path selectors ("match_part" -1 auto / 0 / 1,

@@ -537,6 +537,11 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_pipe(const PmPart* _
 // buffer still fits (131.2 KB).  A 16-lane ds_read_b128 group then holds each
 // (slot, half) four times and its lanes collide when their rows agree mod 4
 // (about 2.6 instead of 2 LDS cycles per group for random rows).
+// npk != 0 (CS 512 only, FOLD_ROT512P): the image is packed (k_fold_image).  Its
+// first npk slices each hold the high halves of 16 coordinate words, whose low
+// halves are zero in every row of the DB and so in every parity; the id slices
+// follow.  The fold itself does not differ: a lane's 8 accumulators of a packed
+// slice are 16 half-words, which the epilogue expands to 16 parity dwords (64 B).
 #ifndef PM_ROT_HPL
 #define PM_ROT_HPL 5
 #endif
@@ -556,8 +561,7 @@ __host__ __device__ constexpr uint32_t rot_nch(uint32_t cs) { return cs == 512 ?
 template <int CS>
 __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __restrict__ parts, uint32_t E,
                                                                 uint32_t nvg, uint32_t nsl, uint32_t npv,
-                                                                uint32_t /* unused; bench.py pins the signature */,
-                                                                uint32_t K, uint32_t ngc) {
+                                                                uint32_t npk_arg, uint32_t K, uint32_t ngc) {
   constexpr uint32_t NCH = rot_nch(CS), LINE = NCH * 8, BUFW = (CS + 1) * LINE;
   constexpr int HPL = rot_hpl(CS);
   static_assert(CS == 512 || CS == 1024, "4 chunks of 512 rows or 2 of 1,024 per block");
@@ -577,6 +581,7 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
   // than HB hints (small configs) keep ngc groups per client instead (no
   // mixing).
   constexpr uint32_t HB = kFoldThreads * HPL;
+  const uint32_t npk = CS == 512 ? npk_arg : 0u;   // packed coordinate slices (nsl counts packed slices)
   const uint32_t xcd = blockIdx.x % 8, kq = blockIdx.x / 8;
   // Order: tiles of GB consecutive (partition, group) pairs x SB consecutive slices,
   // one tile per XCD at a time (GB * SB = its 32 CUs): a group's tabT rows are
@@ -617,7 +622,9 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
   const PM_G uint16_t* const tabA = PA.tabT;
   const PM_G uint16_t* const tabB = PB.tabT;
   const uint32_t hA = cA * H;
-  const uint32_t w = slice * 4, nbuf = SS / NCH;   // SetSize is a multiple of 4 (pir.go:497)
+  // first parity word of the slice: a packed slice covers two 32-B slices of the row
+  const uint32_t w = slice < npk ? slice * 8 : (slice + npk) * 4;
+  const uint32_t nbuf = SS / NCH;   // SetSize is a multiple of 4 (pir.go:497)
   const PM_G char* img = (const PM_G char*)P.img + (uint64_t)slice * nbuf * kRotBufBytes;
   // 16-B reads: lane l reads chunk slot (s + phase) % NCH, halves f then f ^ 1
   // (s = l % NCH, f = (l / NCH) & 1: every ds_read_b128 lane group of 16 holds
@@ -712,11 +719,22 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
     const bool inB = v >= vb;
     PM_G uint64_t* const par = (inB ? PB.parity : PA.parity) + (uint64_t)(v - (inB ? vb : hA)) * E;
     PM_G uint32_t* dst = reinterpret_cast<PM_G uint32_t*>(par + w);
+    if (slice < npk) {   // block-uniform: half-word i of the slice is the high half of parity dword i
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      PM_G uint32_t* const d = dst + 4 * (j ^ (t >> 2)) + (t & 3);
-      if (PM_PREP_NT) __builtin_nontemporal_store(acc[k][t], d);
-      else *d = acc[k][t];
+      for (int t = 0; t < 8; t += 2) {   // accumulators t, t + 1: dwords 2 p .. 2 p + 3 of the 16, p the word's place
+        PM_G u32x4* const d = reinterpret_cast<PM_G u32x4*>(dst + 8 * (j ^ (t >> 2)) + 2 * (t & 3));
+        const u32x4 x = {acc[k][t] << 16, acc[k][t] & 0xffff0000u, acc[k][t + 1] << 16, acc[k][t + 1] & 0xffff0000u};
+        if (PM_PREP_NT) __builtin_nontemporal_store(x, d);
+        else *d = x;
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        PM_G uint32_t* const d = dst + 4 * (j ^ (t >> 2)) + (t & 3);
+        if (PM_PREP_NT) __builtin_nontemporal_store(acc[k][t], d);
+        else *d = acc[k][t];
+      }
     }
     if (w == 0)   // xorSlices leaves the words past len&~3 zero
       for (uint32_t t = E & ~3u; t < E; ++t) par[t] = 0;
@@ -726,19 +744,52 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
 // One partition's fold image: 16-B item it of block (slice s, chunks NCH b..)
 // = line it / (2 NCH), chunk slot (it / 2) % NCH, half it % 2 of row
 // (NCH b + slot) CS + line (NCH = rot_nch(CS); 4,096 items per block).
+// npk != 0, the packed image of a DB whose coordinate words have zero low
+// halves: slice s < npk holds, as 16 consecutive half-words, the high halves of
+// the row's 32-bit words 16 s .. 16 s + 15 (an item: those of 8 words); slice
+// s >= npk is the row's 32-B slice s + npk, whole.  fold_image_src is that map.
+__host__ __device__ inline FoldImageSrc fold_image_src(uint64_t x, uint32_t nbuf, uint32_t CS, uint32_t npk) {
+  const uint32_t lg = CS == 512 ? 2 : 1;   // log2 NCH
+  const uint32_t it = (uint32_t)(x % (kRotBufBytes / 16));
+  const uint64_t blk = x / (kRotBufBytes / 16);
+  const uint32_t b = (uint32_t)(blk % nbuf), s = (uint32_t)(blk / nbuf);
+  FoldImageSrc o;
+  o.row = (uint64_t)((b << lg) + ((it >> 1) & ((1u << lg) - 1))) * CS + (it >> (lg + 1));
+  o.packed = s < npk;
+  o.word = o.packed ? 16 * s + 8 * (it & 1) : 8 * (s + npk) + 4 * (it & 1);
+  return o;
+}
 __global__ void __launch_bounds__(kBlock) k_fold_image(uint4* __restrict__ img, const uint64_t* __restrict__ rows,
                                                       uint64_t N, uint32_t nbuf, uint32_t E, uint64_t nitems,
-                                                      uint32_t CS) {
-  const uint32_t lg = CS == 512 ? 2 : 1;   // log2 NCH
+                                                      uint32_t CS, uint32_t npk) {
   for (uint64_t x = (uint64_t)blockIdx.x * kBlock + threadIdx.x; x < nitems; x += (uint64_t)gridDim.x * kBlock) {
-    const uint32_t it = (uint32_t)(x % (kRotBufBytes / 16));
-    const uint64_t blk = x / (kRotBufBytes / 16);
-    const uint32_t b = (uint32_t)(blk % nbuf), s = (uint32_t)(blk / nbuf);
-    const uint64_t r = (uint64_t)((b << lg) + ((it >> 1) & ((1u << lg) - 1))) * CS + (it >> (lg + 1));
+    const FoldImageSrc src = fold_image_src(x, nbuf, CS, npk);
     uint4 v = make_uint4(0, 0, 0, 0);
-    if (r < N) v = *reinterpret_cast<const uint4*>(rows + r * E + 4 * s + (it & 1) * 2);
+    if (src.row < N) {
+      const uint4* const p = reinterpret_cast<const uint4*>(reinterpret_cast<const uint32_t*>(rows + src.row * E) + src.word);
+      v = p[0];
+      if (src.packed) {
+        const uint4 u = p[1];
+        v = make_uint4((v.x >> 16) | (v.y & 0xffff0000u), (v.z >> 16) | (v.w & 0xffff0000u),
+                       (u.x >> 16) | (u.y & 0xffff0000u), (u.z >> 16) | (u.w & 0xffff0000u));
+      }
+    }
     img[x] = v;
   }
+}
+// OR of the low halves of the coordinate words (32-bit words [0, dim) of every
+// E-word row; dim % 4 == 0, E even): *out becomes non-zero if any is non-zero
+__global__ void __launch_bounds__(kBlock) k_coord_low_or(const uint64_t* __restrict__ rows, uint64_t nrows, uint32_t E,
+                                                        uint32_t dim, uint32_t* __restrict__ out) {
+  const uint32_t per = dim / 4;
+  const uint64_t nitems = nrows * per;
+  uint32_t acc = 0;
+  for (uint64_t x = (uint64_t)blockIdx.x * kBlock + threadIdx.x; x < nitems; x += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t r = x / per;
+    const uint4 v = reinterpret_cast<const uint4*>(rows + r * E)[x - r * per];
+    acc |= v.x | v.y | v.z | v.w;
+  }
+  if (acc & 0xffffu) atomicOr(out, 1u);
 }
 
 // Replacement rows (pir.go:345-350): Qpc random offsets per chunk, idx + copy.
@@ -1063,9 +1114,10 @@ static uint32_t fold_blk_sw(uint32_t maxCS) {
   while (sw > 2 && !fits(sw)) sw /= 2;
   return fits(sw) ? sw : 0;
 }
-int fold_form(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img) {
+int fold_form(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img, uint32_t npk) {
   if ((E & ~3u) == 0) return FOLD_GATHER;   // xorSlices folds nothing: zero parities
-  if (have_img && fold_rot_shape(minCS, maxCS, E)) return maxCS == 512 ? FOLD_ROT512 : FOLD_ROT1024;
+  if (have_img && fold_rot_shape(minCS, maxCS, E))
+    return maxCS == 512 ? (npk ? FOLD_ROT512P : FOLD_ROT512) : FOLD_ROT1024;
   if (minCS == maxCS && (maxCS == 512 || maxCS == 1024 || maxCS == 2048) && E % 2 == 0) return FOLD_PIPE;
   if (E % 2 || !fold_blk_sw(maxCS)) return FOLD_GATHER;   // odd entries or very wide chunks
   return FOLD_BLK;
@@ -1076,22 +1128,55 @@ bool fold_needs_tab(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img) {
   const int form = fold_form(minCS, maxCS, E, have_img);
   return form == FOLD_PIPE || form == FOLD_BLK;
 }
-uint64_t fold_image_words(uint32_t SS, uint32_t E, uint32_t CS) {
-  return (uint64_t)(E / 4) * (SS / rot_nch(CS)) * (kRotBufBytes / 8);
+static std::atomic<int> g_fold_pack{-1};
+void set_fold_pack(int v) { g_fold_pack.store(v < 0 ? -1 : (v ? 1 : 0)); }
+// Like "fold_rot", "fold_pack" (else PM_FOLD_PACK, default on) is read here
+// only, while a server's image is built; its clients share the image and so the
+// decision.  Whole packed slices: 16 coordinate words each, inside the folded
+// E & ~3 words.
+uint32_t fold_pack_slices(uint32_t minCS, uint32_t maxCS, uint32_t E, uint32_t dim) {
+  static const bool env = [] { const char* e = getenv("PM_FOLD_PACK"); return !e || e[0] != '0'; }();
+  const int v = g_fold_pack.load();
+  if (!(v < 0 ? env : v == 1) || fold_form(minCS, maxCS, E, true) != FOLD_ROT512) return 0;
+  return fold_pack_shape(E, dim);
 }
-void fold_image(hipStream_t st, uint64_t* img, const uint64_t* rows, uint64_t N, uint32_t SS, uint32_t E, uint32_t CS) {
-  const uint64_t nitems = fold_image_words(SS, E, CS) / 2;
+uint32_t fold_pack_shape(uint32_t E, uint32_t dim) {
+  return dim && dim % 16 == 0 && dim / 8 <= E / 4 ? dim / 16 : 0;
+}
+bool coord_low_zero(hipStream_t st, const uint64_t* rows, uint64_t nrows, uint32_t E, uint32_t dim, uint32_t* flag) {
+  if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return false;
+  unsigned grid = cdiv(nrows * (dim / 4), kBlock);
+  if (grid > 256 * 32) grid = 256 * 32;
+  if (grid) hipLaunchKernelGGL(k_coord_low_or, dim3(grid), dim3(kBlock), 0, st, rows, nrows, E, dim, flag);
+  uint32_t h = 1;
+  if (hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return false;
+  return h == 0;
+}
+uint64_t fold_image_words(uint32_t SS, uint32_t E, uint32_t CS, uint32_t npk) {
+  return (uint64_t)(E / 4 - npk) * (SS / rot_nch(CS)) * (kRotBufBytes / 8);
+}
+void fold_image(hipStream_t st, uint64_t* img, const uint64_t* rows, uint64_t N, uint32_t SS, uint32_t E, uint32_t CS,
+                uint32_t npk) {
+  const uint64_t nitems = fold_image_words(SS, E, CS, npk) / 2;
   unsigned grid = cdiv(nitems, kBlock);
   if (grid > 256 * 32) grid = 256 * 32;
   hipLaunchKernelGGL(k_fold_image, dim3(grid), dim3(kBlock), 0, st, (uint4*)img, rows, N, SS / rot_nch(CS), E, nitems,
-                     CS);
+                     CS, npk);
+}
+void fold_image_map(uint32_t CS, uint32_t SS, uint32_t npk, uint64_t x0, uint64_t n, uint64_t* row, uint32_t* word,
+                    uint8_t* packed) {
+  for (uint64_t i = 0; i < n; ++i) {
+    const FoldImageSrc s = fold_image_src(x0 + i, SS / rot_nch(CS), CS, npk);
+    row[i] = s.row; word[i] = s.word; packed[i] = s.packed;
+  }
 }
 int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint64_t* db, uint32_t E,
               uint32_t minCS, uint32_t maxCS, const uint64_t* zero16, uint32_t clients, bool have_img,
-               uint32_t minH) {
+               uint32_t minH, uint32_t npk) {
   // the form follows from what the engine was created with (have_img) and the
   // shape alone (fold_form): the same inputs that decided whether PmPart::tab exists
-  const int form = fold_form(minCS, maxCS, E, have_img);
+  const int form = fold_form(minCS, maxCS, E, have_img, npk);
   const uint32_t EX = E & ~3u;
   if (EX == 0) {
     hipLaunchKernelGGL(k_prep_fold<2>, dim3(cdiv((uint64_t)maxH * E, kBlock), np), dim3(kBlock), 0,
@@ -1107,9 +1192,10 @@ int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint
     else if (sw == 4) hipLaunchKernelGGL(k_prep_fold_blk<4>, grid, blk, lds, st, d, db, zero16, E, w0);
     else hipLaunchKernelGGL(k_prep_fold_blk<2>, grid, blk, lds, st, d, db, zero16, E, w0);
   };
-  if (form == FOLD_ROT512 || form == FOLD_ROT1024 || form == FOLD_PIPE) {
+  if (form == FOLD_ROT512 || form == FOLD_ROT512P || form == FOLD_ROT1024 || form == FOLD_PIPE) {
     // (SW, G): CS 512 -> (4, 1), 1024 -> (4, 2), 2048 -> (2, 2); EX % SW == 0
-    const uint32_t psw = maxCS == 2048 ? 2 : 4, nsl = EX / psw;
+    // the packed image: npk slices in place of the 2 npk coordinate slices
+    const uint32_t psw = maxCS == 2048 ? 2 : 4, nsl = EX / psw - (form == FOLD_ROT512P ? npk : 0);
     const uint32_t K = clients && np % clients == 0 ? clients : 1, npg = (np / K) * ng;
     const uint32_t lw = 16 / psw, per_pg = K * cdiv(nsl, lw) * lw;
 #ifndef PM_FOLD_NB512
@@ -1123,10 +1209,12 @@ int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint
       const uint64_t HB = (uint64_t)kFoldThreads * rot_hpl(maxCS);
       const uint32_t ngc = minH >= HB ? 0u : (uint32_t)cdiv(maxH, HB);
       const uint32_t nvg = ngc ? K * ngc : (uint32_t)cdiv((uint64_t)K * maxH, HB), npv = (np / K) * nvg;
-      // whole tiles of GB pairs x SB slices, dealt over the 8 XCDs (the kernel's fifth parameter is unused)
+      // whole tiles of GB pairs x SB slices, dealt over the 8 XCDs (the kernel's sixth parameter: the packed
+      // coordinate slices, 0 for the plain image)
       const uint32_t grid = 8 * cdiv((uint64_t)cdiv(npv, PM_ROT_GB) * cdiv(nsl, PM_ROT_SB), 8) * PM_ROT_GB * PM_ROT_SB;
-      if (form == FOLD_ROT512)
-        hipLaunchKernelGGL(k_prep_fold_rot<512>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, 0u, K, ngc);
+      if (form != FOLD_ROT1024)
+        hipLaunchKernelGGL(k_prep_fold_rot<512>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv,
+                           form == FOLD_ROT512P ? npk : 0u, K, ngc);
       else
         hipLaunchKernelGGL(k_prep_fold_rot<1024>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, 0u, K, ngc);
       return form;

@@ -136,7 +136,7 @@ extern "C" int pm_graph_preprocess(pm_graph* g) {
     pm_batchpir* h = new pm_batchpir();
     const DbGen gen{1, g->data_seed, (uint32_t)g->dim, (uint32_t)g->m};
     if (int r = engine_create(g->ctx, &h->e, g->n, ebytes, g->m, nullptr, 8, g->pir_seed, true, g->shard, g->nshards,
-                              nullptr, &gen)) { delete h; return r; }
+                              nullptr, &gen, (uint32_t)g->dim)) { delete h; return r; }
     g->pir = h;
     g->pir->e.pf_off = g->dim * 4;
     g->pir->e.pf_len = g->m * 4;
@@ -151,8 +151,11 @@ extern "C" int pm_graph_preprocess(pm_graph* g) {
       memcpy(e + g->dim * 4, &g->graph[i * g->m], g->m * 4);
     }
     delete g->pir; g->pir = nullptr;
-    CHK(pm_batchpir_create_shard(g->ctx, g->n, ebytes, g->m, raw.data(), 8, g->pir_seed, g->shard, g->nshards,
-                                 &g->pir));
+    // as pm_batchpir_create_shard, with the entry layout: words [0, dim) are the coordinates
+    pm_batchpir* h = new pm_batchpir();
+    if (int r = engine_create(g->ctx, &h->e, g->n, ebytes, g->m, raw.data(), 8, g->pir_seed, true, g->shard, g->nshards,
+                              nullptr, nullptr, (uint32_t)g->dim)) { delete h; return r; }
+    g->pir = h;
     g->pir->e.pf_off = g->dim * 4;   // the search reads the neighbour lists of the rows
     g->pir->e.pf_len = g->m * 4;
     if (g->skipPrep) CHK(pm_batchpir_dummy_preprocessing(g->pir));
