@@ -501,7 +501,8 @@ int pm_knn(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, const float
  * every other row is answered again by a brute-force kernel (slow: n dim
  * operations per row).  *fallback_rows (nullable): rows answered by the
  * brute-force kernel instead of the certified prefilter.  Non-finite inputs
- * get some answer through the fallback.  Arguments as pm_knn; dim <= 192. */
+ * get some answer through the fallback.  Arguments as pm_knn; dim <= 192
+ * (pm_knn_wide takes rows up to 1,024). */
 int pm_knn_exact(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
                  uint32_t k, int64_t* ids, float* dists, uint64_t* fallback_rows);
 /* BuildGraph / CreateGraphBasedOnNGT (build_graph.go:97-105,314-523) with the
@@ -557,6 +558,38 @@ int pm_knn_stages(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, cons
 int pm_robust_prune(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* verts,
                     uint64_t nverts, const uint64_t* offs, const uint32_t* lens, const uint32_t* ids, uint64_t nids,
                     uint32_t m, float alpha, int presorted, uint32_t* out, uint32_t* out_len, uint32_t* err);
+
+/* ---- rows up to 1,024 dimensions --------------------- */
+/* The four calls below are pm_knn_exact, pm_build_graph_exact, pm_knn_stages
+ * (exact form) and pm_robust_prune for dim in [1, 1024]; every other argument
+ * rule is the narrow call's (k in [1, 64]; m in [1, 42] for the build and
+ * [1, 64] for the prune probe).  dim = 0 or dim > 1024 gives PM_EINVAL, "dim
+ * must be in [1, 1024]", before any HIP call.  For dim <= 192 they run the
+ * narrow calls' kernels unchanged, so a caller needs only these names.  For
+ * dim in [193, 1024] the rows are padded to the next multiple of 64 (dp) and
+ * the prefilter walks them in chunks of 64 (k_knn_bf16x3_w, timing name
+ * "knn_prefilter_w"); the fallback and robustPrune keep one row in LDS
+ * (k_knn_brute_w, k_prune_w).  Only the exact (certified) form exists for wide
+ * rows: pm_knn's promise for integer rows needs dim * 255^2 < 2^24, i.e. dim
+ * <= 258.  The certificate's eps is c_dp (|q|^2 + max |x|^2) + 2^-50 with c_dp =
+ * 2 (3 dp + 8) 2^-23 + 2^-16 (1 + 2^-6) + 2^-17: 2.08e-4 at dp 256, 3.91e-4 at
+ * 512, 7.57e-4 at 1,024, above the 2^-12 quoted for the narrow path, so wide
+ * rows reach the brute-force kernel more often on tightly clustered data.
+ * The result is the brute-force (L2Dist in l2_distance_amd64.s order, id)
+ * ranking for every finite float input either way. */
+int pm_knn_wide(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                uint32_t k, int64_t* ids, float* dists, uint64_t* fallback_rows);
+/* pm_build_graph_exact for dim in [1, 1024], m <= 42: equals the oracle's graph. */
+int pm_build_graph_wide(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
+                        uint64_t seed, uint32_t* graph, double* times, uint64_t* fallback_rows);
+/* Test probes: pm_knn_stages' exact form (out->dp reports the padded width:
+ * 128, 192 or the next multiple of 64) and pm_robust_prune. */
+int pm_knn_stages_wide(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                       uint32_t k, pm_knn_stages_out* out);
+int pm_robust_prune_wide(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* verts,
+                         uint64_t nverts, const uint64_t* offs, const uint32_t* lens, const uint32_t* ids,
+                         uint64_t nids, uint32_t m, float alpha, int presorted, uint32_t* out, uint32_t* out_len,
+                         uint32_t* err);
 
 #ifdef __cplusplus
 }

@@ -143,6 +143,11 @@ SIGNATURES = {
     "pm_knn_stages": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, C.c_int, C.POINTER(KnnStagesOut)]),
     "pm_robust_prune": (C.c_int, [vp, f32p, u64, u64, u32p, u64, u64p, u32p, u32p, u64, C.c_uint32, C.c_float, C.c_int,
                                   u32p, u32p, u32p]),
+    "pm_knn_wide": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, i64p, f32p, u64p]),
+    "pm_build_graph_wide": (C.c_int, [vp, f32p, u64, u64, u64, C.c_float, u64, u32p, C.POINTER(dbl), u64p]),
+    "pm_knn_stages_wide": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, C.POINTER(KnnStagesOut)]),
+    "pm_robust_prune_wide": (C.c_int, [vp, f32p, u64, u64, u32p, u64, u64p, u32p, u32p, u64, C.c_uint32, C.c_float,
+                                       C.c_int, u32p, u32p, u32p]),
     "pm_search_loop_sessions": (C.c_int, [C.POINTER(vp), C.c_uint32, f32p, u64, C.c_int, C.c_int, C.c_int,
                                           i64p, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "pm_batchpir_group_create": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
@@ -913,18 +918,33 @@ def knn_exact(base, queries, k: int, ctx: Context | None = None, with_dist: bool
     """pm.knn, exact for every finite float input (pm_knn_exact).  Returns
     (ids[, dists], fallback_rows): fallback_rows query rows were answered by the
     brute-force kernel because the prefilter's certificate did not hold."""
+    return _knn_exact(lib().pm_knn_exact, base, queries, k, ctx, with_dist)
+
+
+def knn_wide(base, queries, k: int, ctx: Context | None = None, with_dist: bool = False):
+    """pm.knn_exact for rows of 1 to 1,024 dimensions (pm_knn_wide)."""
+    return _knn_exact(lib().pm_knn_wide, base, queries, k, ctx, with_dist)
+
+
+def _knn_exact(fn, base, queries, k, ctx, with_dist):
     ctx = ctx or default_context()
     b = np.ascontiguousarray(base, dtype=np.float32)
     q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, b.shape[1])
     ids = np.zeros((q.shape[0], k), dtype=np.int64)
     d = np.zeros((q.shape[0], k), dtype=np.float32)
     fb = u64(0)
-    _check(lib().pm_knn_exact(ctx.h, _p(b, f32p), b.shape[0], b.shape[1], _p(q, f32p), q.shape[0], k, _p(ids, i64p),
-                              _p(d, f32p), C.byref(fb)))
+    _check(fn(ctx.h, _p(b, f32p), b.shape[0], b.shape[1], _p(q, f32p), q.shape[0], k, _p(ids, i64p), _p(d, f32p),
+              C.byref(fb)))
     return (ids, d, int(fb.value)) if with_dist else (ids, int(fb.value))
 
 
-def knn_stages(base, queries, k: int, ctx: Context | None = None, exact: bool = True) -> dict:
+def knn_stages_wide(base, queries, k: int, ctx: Context | None = None) -> dict:
+    """pm_knn_stages_wide: pm.knn_stages' exact form for rows of 1 to 1,024
+    dimensions; "dp" is 128, 192 or, above 192, the next multiple of 64."""
+    return knn_stages(base, queries, k, ctx, exact=True, wide=True)
+
+
+def knn_stages(base, queries, k: int, ctx: Context | None = None, exact: bool = True, wide: bool = False) -> dict:
     """pm_knn_stages: what pm.knn (exact=False) or pm.knn_exact keeps inside for
     these rows.  "cand" [nq, 64] uint32 (0xffffffff: empty slot) and "pref"
     [nq, 64] float32, the prefilter's keys in order, and "dp"; exact adds "tau",
@@ -934,6 +954,8 @@ def knn_stages(base, queries, k: int, ctx: Context | None = None, exact: bool = 
     b = np.ascontiguousarray(base, dtype=np.float32)
     q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, b.shape[1])
     n, nq, dp = b.shape[0], q.shape[0], 192 if b.shape[1] > 128 else 128
+    if wide and b.shape[1] > 192:
+        dp = -(-b.shape[1] // 64) * 64
     r = {"cand": np.zeros((nq, 64), np.uint32), "pref": np.zeros((nq, 64), np.float32)}
     if exact:
         r.update(tau=np.zeros(nq, np.float32), eps=np.zeros(nq, np.float32), qnorm=np.zeros(nq, np.float32),
@@ -943,7 +965,10 @@ def knn_stages(base, queries, k: int, ctx: Context | None = None, exact: bool = 
     for name, ctype in KnnStagesOut._fields_:
         if name in r:
             setattr(o, name, _p(r[name], ctype))
-    _check(lib().pm_knn_stages(ctx.h, _p(b, f32p), n, b.shape[1], _p(q, f32p), nq, k, int(exact), C.byref(o)))
+    if wide:
+        _check(lib().pm_knn_stages_wide(ctx.h, _p(b, f32p), n, b.shape[1], _p(q, f32p), nq, k, C.byref(o)))
+    else:
+        _check(lib().pm_knn_stages(ctx.h, _p(b, f32p), n, b.shape[1], _p(q, f32p), nq, k, int(exact), C.byref(o)))
     assert o.dp == dp
     r["dp"] = dp
     if exact:
@@ -952,8 +977,14 @@ def knn_stages(base, queries, k: int, ctx: Context | None = None, exact: bool = 
     return r
 
 
+def robust_prune_wide(vectors, verts, lists, m: int, alpha: float = 1.2, presorted: bool = False,
+                      ctx: Context | None = None):
+    """pm.robust_prune for rows of 1 to 1,024 dimensions (pm_robust_prune_wide)."""
+    return robust_prune(vectors, verts, lists, m, alpha, presorted, ctx, wide=True)
+
+
 def robust_prune(vectors, verts, lists, m: int, alpha: float = 1.2, presorted: bool = False,
-                 ctx: Context | None = None):
+                 ctx: Context | None = None, wide: bool = False):
     """pm_robust_prune: robustPrune of lists[b], the candidates of vertex
     verts[b] (distinct), on the GPU.  Returns (one uint32 array per list, err)."""
     ctx = ctx or default_context()
@@ -967,14 +998,20 @@ def robust_prune(vectors, verts, lists, m: int, alpha: float = 1.2, presorted: b
     out = np.zeros((len(vs), m), dtype=np.uint32)
     ol = np.zeros(len(vs), dtype=np.uint32)
     err = np.zeros(1, dtype=np.uint32)
-    _check(lib().pm_robust_prune(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], _p(vs, u32p), len(vs), _p(offs, u64p),
-                                 _p(lens, u32p), _p(ids, u32p), len(ids), m, alpha, int(presorted), _p(out, u32p),
-                                 _p(ol, u32p), _p(err, u32p)))
+    fn = lib().pm_robust_prune_wide if wide else lib().pm_robust_prune
+    _check(fn(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], _p(vs, u32p), len(vs), _p(offs, u64p), _p(lens, u32p),
+              _p(ids, u32p), len(ids), m, alpha, int(presorted), _p(out, u32p), _p(ol, u32p), _p(err, u32p)))
     return [out[b, :ol[b]].copy() for b in range(len(vs))], int(err[0])
 
 
+def build_graph_wide(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context | None = None):
+    """pm.build_graph(exact=True) for rows of 1 to 1,024 dimensions
+    (pm_build_graph_wide)."""
+    return build_graph(vectors, m, alpha, seed, ctx, exact=True, wide=True)
+
+
 def build_graph(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context | None = None,
-                exact: bool = False):
+                exact: bool = False, wide: bool = False):
     """graphann.BuildGraph (build_graph.go:97-105,314-523) on the GPU with exact
     kNN candidates (pm_build_graph).  Returns (graph [n, m] uint32, times dict).
     exact=True: pm_build_graph_exact, whose candidates are exact for general
@@ -985,8 +1022,8 @@ def build_graph(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context
     t = (dbl * 4)()
     fb = u64(0)
     if exact:
-        _check(lib().pm_build_graph_exact(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], m, alpha, seed, _p(g, u32p), t,
-                                          C.byref(fb)))
+        fn = lib().pm_build_graph_wide if wide else lib().pm_build_graph_exact
+        _check(fn(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], m, alpha, seed, _p(g, u32p), t, C.byref(fb)))
     else:
         _check(lib().pm_build_graph(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], m, alpha, seed, _p(g, u32p), t))
     times = {"knn_s": t[0], "prune1_s": t[1], "host_edges_s": t[2], "prune2_s": t[3]}

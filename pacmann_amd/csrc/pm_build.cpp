@@ -30,9 +30,15 @@ struct KnnDev {   // device copies for the prefilter + re-rank
   DevBuf x, xb, xl, xn, mx;   // f32 rows, bf16 rows (exact: hi), exact: lo, norms, exact: the largest norm's bits
   uint32_t dp = 0;
 };
-// exact: the split rows of pm_knn_exact (hi + lo, norms of the f32 values)
-static int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDev& d, bool exact) {
-  d.dp = pmk::knn_pad_dim(dim);
+// The "_wide" entry points: rows up to 1,024 wide.  Up to kWideFrom they take the
+// narrow path unchanged; above it the kernels of pm_graph_wide.hip.
+static const char* const kWideDimText = "dim must be in [1, 1024]";
+constexpr uint32_t kWideFrom = 192;
+static bool wide_dim_ok(uint64_t dim) { return pmk::knn_pad_dim_wide((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)) != 0; }
+// exact: the split rows of pm_knn_exact (hi + lo, norms of the f32 values);
+// wide (exact only): rows above kWideFrom are padded by knn_pad_dim_wide
+static int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDev& d, bool exact, bool wide = false) {
+  d.dp = wide && dim > kWideFrom ? pmk::knn_pad_dim_wide(dim) : pmk::knn_pad_dim(dim);
   if (!d.dp) return fail(PM_EINVAL, "kNN supports dim <= 192");
   CHK(d.x.reserve(std::max<uint64_t>(4, n * dim * 4)));
   CHK(d.xb.reserve(std::max<uint64_t>(4, n * d.dp * 2)));
@@ -92,9 +98,15 @@ static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, u
     CHK(o.eps.reserve(std::max<uint64_t>(4, nq * 4)));
     HIPCHK(hipMemsetAsync(o.eps.p, 0xff, std::max<uint64_t>(4, nq * 4), st));
   }
-  c->timed("knn_prefilter_x3", 2 * pre_bytes, [&] {
-    pmk::knn_prefilter_x3(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
-                          o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
+  const bool wide = B.dp > kWideFrom;   // rows padded by knn_pad_dim_wide: the kernels of pm_graph_wide.hip
+  if (wide)
+    c->timed("knn_prefilter_w", 2 * pre_bytes, [&] {
+      pmk::knn_prefilter_x3_w(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
+                              o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
+  else
+    c->timed("knn_prefilter_x3", 2 * pre_bytes, [&] {
+      pmk::knn_prefilter_x3(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
+                            o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
   c->timed("knn_rerank", rr_bytes, [&] {
     pmk::knn_rerank_cert(st, B.x.as<float>(), n, dim, Q.x.as<float>(), nq, o.cand.as<uint32_t>(), K, self_base,
                          o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>(), Q.xn.as<float>(),
@@ -104,8 +116,9 @@ static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, u
   HIPCHK(hipMemcpyAsync(&nl, o.nlist.p, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   c->timed("knn_brute", (double)nl * n * dim * 4, [&] {
-    pmk::knn_brute(st, B.x.as<float>(), n, dim, Q.x.as<float>(), o.list.as<uint64_t>(), nl, K, self_base,
-                   o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>()); });
+    (wide ? pmk::knn_brute_w : pmk::knn_brute)(st, B.x.as<float>(), n, dim, Q.x.as<float>(), o.list.as<uint64_t>(), nl,
+                                               K, self_base, o.out.as<uint32_t>(), o.dist.as<float>(),
+                                               o.len.as<uint32_t>()); });
   HIPCHK(hipStreamSynchronize(st));
   o.nl = nl;
   if (fallback) *fallback = nl;
@@ -116,16 +129,17 @@ static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, u
 // id), k <= 64 (the ground truth of ComputeRecall, build_graph.go:821-863);
 // ids -1 padded.
 static int knn_impl(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
-                    uint32_t k, int64_t* ids, float* dists, bool exact, uint64_t* fallback) {
+                    uint32_t k, int64_t* ids, float* dists, bool exact, uint64_t* fallback, bool wide = false) {
   if (!c || !base || (!queries && nq) || (!ids && nq)) return fail(PM_EINVAL, "NULL argument");
+  if (wide && !wide_dim_ok(dim)) return fail(PM_EINVAL, kWideDimText);
   if (k == 0 || k > pmk::knn_top()) return fail(PM_EINVAL, "k must be in [1, 64]");
   if (n == 0 || dim == 0 || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be in [1, 2^32-1)");
-  if (exact && !pmk::knn_pad_dim((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)))
+  if (exact && !wide && !pmk::knn_pad_dim((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)))
     return fail(PM_EINVAL, "kNN supports dim <= 192");
   HIPCHK(hipSetDevice(c->device));
   KnnDev B, Q;
-  CHK(knn_upload(c, base, n, (uint32_t)dim, B, exact));
-  CHK(knn_upload(c, queries, nq, (uint32_t)dim, Q, exact));
+  CHK(knn_upload(c, base, n, (uint32_t)dim, B, exact, wide));
+  CHK(knn_upload(c, queries, nq, (uint32_t)dim, Q, exact, wide));
   KnnOut o;
   CHK(knn_device(c, B, n, Q, nq, (uint32_t)dim, k, false, true, exact, o, fallback));
   std::vector<uint32_t> out(nq * k), l(nq);
@@ -150,22 +164,29 @@ extern "C" int pm_knn_exact(pm_ctx* c, const float* base, uint64_t n, uint64_t d
   if (fallback_rows) *fallback_rows = 0;
   return knn_impl(c, base, n, dim, queries, nq, k, ids, dists, true, fallback_rows);
 }
+extern "C" int pm_knn_wide(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                           uint32_t k, int64_t* ids, float* dists, uint64_t* fallback_rows) {
+  if (fallback_rows) *fallback_rows = 0;
+  return knn_impl(c, base, n, dim, queries, nq, k, ids, dists, true, fallback_rows, true);
+}
 
-// pm_knn_stages: pm_knn's (exact: pm_knn_exact's) own upload and launches
-// (knn_upload, knn_device), with the intermediate values copied out.
-extern "C" int pm_knn_stages(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries,
-                             uint64_t nq, uint32_t k, int exact, pm_knn_stages_out* out) {
+// pm_knn_stages and pm_knn_stages_wide: pm_knn's (exact: pm_knn_exact's, wide:
+// pm_knn_wide's) own upload and launches (knn_upload, knn_device), with the
+// intermediate values copied out.
+static int knn_stages_impl(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                           uint32_t k, int exact, pm_knn_stages_out* out, bool wide) {
   if (!c || !base || !queries || !out || !out->cand || !out->pref) return fail(PM_EINVAL, "NULL argument");
+  if (wide && !wide_dim_ok(dim)) return fail(PM_EINVAL, kWideDimText);
   if (k == 0 || k > pmk::knn_top()) return fail(PM_EINVAL, "k must be in [1, 64]");
   if (n == 0 || dim == 0 || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be in [1, 2^32-1)");
   if (nq == 0) return fail(PM_EINVAL, "nq must be > 0");
-  if (!pmk::knn_pad_dim((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)))
+  if (!wide && !pmk::knn_pad_dim((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)))
     return fail(PM_EINVAL, "kNN supports dim <= 192");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
   KnnDev B, Q;
-  CHK(knn_upload(c, base, n, (uint32_t)dim, B, exact != 0));
-  CHK(knn_upload(c, queries, nq, (uint32_t)dim, Q, exact != 0));
+  CHK(knn_upload(c, base, n, (uint32_t)dim, B, exact != 0, wide));
+  CHK(knn_upload(c, queries, nq, (uint32_t)dim, Q, exact != 0, wide));
   KnnOut o;
   o.stages = true;
   CHK(knn_device(c, B, n, Q, nq, (uint32_t)dim, k, false, true, exact != 0, o, nullptr));
@@ -197,6 +218,14 @@ extern "C" int pm_knn_stages(pm_ctx* c, const float* base, uint64_t n, uint64_t 
   }
   return 0;
 }
+extern "C" int pm_knn_stages(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries,
+                             uint64_t nq, uint32_t k, int exact, pm_knn_stages_out* out) {
+  return knn_stages_impl(c, base, n, dim, queries, nq, k, exact, out, false);
+}
+extern "C" int pm_knn_stages_wide(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries,
+                                  uint64_t nq, uint32_t k, pm_knn_stages_out* out) {
+  return knn_stages_impl(c, base, n, dim, queries, nq, k, 1, out, true);
+}
 
 // robustPrune on the GPU of the listed vertices' lists (the second pass of the
 // build, :464-466; pm_robust_prune): vertex u's candidates are conn[coff[u] ..
@@ -210,7 +239,9 @@ extern "C" int pm_knn_stages(pm_ctx* c, const float* base, uint64_t n, uint64_t 
 static int prune_lists(pm_ctx* c, const float* X, uint64_t n, uint32_t dim, const std::vector<uint32_t>& big,
                        const std::vector<uint32_t>& huge, const std::vector<uint64_t>& coff,
                        const std::vector<uint32_t>& clen, const std::vector<uint32_t>& conn, uint32_t m, float alpha,
-                       std::vector<uint32_t>& P, std::vector<uint32_t>& PL, uint32_t* e) {
+                       std::vector<uint32_t>& P, std::vector<uint32_t>& PL, uint32_t* e, bool wide = false) {
+  // wide: rows above kWideFrom go to k_prune_w (the same lists, results and error flag)
+  const auto prune = wide && dim > kWideFrom ? pmk::prune_w : pmk::prune;
   *e = 0;
   if (big.empty() && huge.empty()) return 0;
   hipStream_t st = c->stream;
@@ -229,8 +260,9 @@ static int prune_lists(pm_ctx* c, const float* X, uint64_t n, uint32_t dim, cons
   HIPCHK(hipMemcpyAsync(dlen.p, clen.data(), n * 4, hipMemcpyHostToDevice, st));
   if (!conn.empty()) HIPCHK(hipMemcpyAsync(dids.p, conn.data(), conn.size() * 4, hipMemcpyHostToDevice, st));
   c->timed("prune", 0.0, [&] {
-    pmk::prune(st, X, dim, dv.as<uint32_t>(), big.size(), doff.as<uint64_t>(), 0, dlen.as<uint32_t>(),
-               dids.as<uint32_t>(), m, alpha, dout.as<uint32_t>(), dol.as<uint32_t>(), err.as<uint32_t>()); });
+    prune(st, X, dim, dv.as<uint32_t>(), big.size(), doff.as<uint64_t>(), 0, dlen.as<uint32_t>(),
+          dids.as<uint32_t>(), m, alpha, dout.as<uint32_t>(), dol.as<uint32_t>(), err.as<uint32_t>(), nullptr,
+          nullptr); });
   if (!huge.empty()) {
     CHK(dd.reserve(std::max<uint64_t>(4, conn.size() * 4)));
     CHK(dpos.reserve(std::max<uint64_t>(4, conn.size() * 4)));
@@ -258,9 +290,9 @@ static int prune_lists(pm_ctx* c, const float* X, uint64_t n, uint32_t dim, cons
     });
     if (!pos.empty()) HIPCHK(hipMemcpyAsync(dpos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, st));
     c->timed("prune", 0.0, [&] {
-      pmk::prune(st, X, dim, dh.as<uint32_t>(), huge.size(), doff.as<uint64_t>(), 0, dlen.as<uint32_t>(),
-                 dids.as<uint32_t>(), m, alpha, dout.as<uint32_t>(), dol.as<uint32_t>(), err.as<uint32_t>(),
-                 dpos.as<uint32_t>(), dd.as<float>()); });
+      prune(st, X, dim, dh.as<uint32_t>(), huge.size(), doff.as<uint64_t>(), 0, dlen.as<uint32_t>(),
+            dids.as<uint32_t>(), m, alpha, dout.as<uint32_t>(), dol.as<uint32_t>(), err.as<uint32_t>(),
+            dpos.as<uint32_t>(), dd.as<float>()); });
   }
   P.resize(n * m);
   PL.resize(n);
@@ -273,19 +305,21 @@ static int prune_lists(pm_ctx* c, const float* X, uint64_t n, uint32_t dim, cons
 
 // pm_build_graph and pm_build_graph_exact
 static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
-                            uint64_t seed, uint32_t* graph, double* times, bool exact, uint64_t* fallback) {
+                            uint64_t seed, uint32_t* graph, double* times, bool exact, uint64_t* fallback,
+                            bool wide = false) {
   if (!c || !vectors || !graph) return fail(PM_EINVAL, "NULL argument");
+  if (wide && !wide_dim_ok(dim)) return fail(PM_EINVAL, kWideDimText);
   const uint32_t K = (uint32_t)((float)m * 1.5f);   // int(float32(m)*1.5) NGT results (build_graph.go:398)
   if (m == 0 || m > pmk::prune_max_m() || K + 1 > pmk::knn_top())
     return fail(PM_EINVAL, "m must be in [1, 42] (1.5 m candidates + self within the 64-key prefilter)");
-  if (dim == 0 || dim > pmk::prune_max_dim() || !pmk::knn_pad_dim((uint32_t)dim))
+  if (!wide && (dim == 0 || dim > pmk::prune_max_dim() || !pmk::knn_pad_dim((uint32_t)dim)))
     return fail(PM_EINVAL, "dim must be in [1, 192]");
   if (n <= m || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be > m (the random fill needs m other vertices)");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
   auto t0 = Clock::now();
   KnnDev X;
-  CHK(knn_upload(c, vectors, n, (uint32_t)dim, X, exact));
+  CHK(knn_upload(c, vectors, n, (uint32_t)dim, X, exact, wide));
   KnnOut kn;
   DevBuf g1, len1, err;
   CHK(g1.reserve(n * m * 4));
@@ -298,8 +332,9 @@ static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_
   auto t1 = Clock::now();
   // first pass: robustPrune(vectors, u, candidates, m, alpha) (:413-414)
   c->timed("prune", 0.0, [&] {
-    pmk::prune(st, X.x.as<float>(), (uint32_t)dim, nullptr, n, nullptr, K, kn.len.as<uint32_t>(), kn.out.as<uint32_t>(),
-               (uint32_t)m, alpha, g1.as<uint32_t>(), len1.as<uint32_t>(), err.as<uint32_t>()); });
+    (wide && dim > kWideFrom ? pmk::prune_w : pmk::prune)(
+        st, X.x.as<float>(), (uint32_t)dim, nullptr, n, nullptr, K, kn.len.as<uint32_t>(), kn.out.as<uint32_t>(),
+        (uint32_t)m, alpha, g1.as<uint32_t>(), len1.as<uint32_t>(), err.as<uint32_t>(), nullptr, nullptr); });
   std::vector<uint32_t> G(n * m), L1(n);
   uint32_t e = 0;
   HIPCHK(hipMemcpyAsync(G.data(), g1.p, n * m * 4, hipMemcpyDeviceToHost, st));
@@ -362,7 +397,8 @@ static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_
   auto t3 = Clock::now();
   if (!big.empty() || !huge.empty()) {
     std::vector<uint32_t> P, PL;
-    CHK(prune_lists(c, X.x.as<float>(), n, (uint32_t)dim, big, huge, coff, clen2, conn, (uint32_t)m, alpha, P, PL, &e));
+    CHK(prune_lists(c, X.x.as<float>(), n, (uint32_t)dim, big, huge, coff, clen2, conn, (uint32_t)m, alpha, P, PL, &e,
+                    wide));
     if (e) return fail(PM_EINVAL, "robustPrune: a connection list above the kernel's limit");
     for (const auto* lst : {&big, &huge})
       for (uint32_t u : *lst) {   // robustPrune of a list > m returns exactly m
@@ -404,17 +440,24 @@ extern "C" int pm_build_graph_exact(pm_ctx* c, const float* vectors, uint64_t n,
   if (fallback_rows) *fallback_rows = 0;
   return build_graph_impl(c, vectors, n, dim, m, alpha, seed, graph, times, true, fallback_rows);
 }
+extern "C" int pm_build_graph_wide(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
+                                   uint64_t seed, uint32_t* graph, double* times, uint64_t* fallback_rows) {
+  if (fallback_rows) *fallback_rows = 0;
+  return build_graph_impl(c, vectors, n, dim, m, alpha, seed, graph, times, true, fallback_rows, true);
+}
 
-// pm_robust_prune: k_prune on given lists, through the build's own second pass
-// (prune_lists); every list by the LDS sort, or every list presorted.
-extern "C" int pm_robust_prune(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* verts,
-                               uint64_t nverts, const uint64_t* offs, const uint32_t* lens, const uint32_t* ids,
-                               uint64_t nids, uint32_t m, float alpha, int presorted, uint32_t* out,
-                               uint32_t* out_len, uint32_t* err) {
+// pm_robust_prune and pm_robust_prune_wide: k_prune (wide, rows above kWideFrom:
+// k_prune_w) on given lists, through the build's own second pass (prune_lists);
+// every list by the LDS sort, or every list presorted.
+static int robust_prune_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* verts,
+                             uint64_t nverts, const uint64_t* offs, const uint32_t* lens, const uint32_t* ids,
+                             uint64_t nids, uint32_t m, float alpha, int presorted, uint32_t* out, uint32_t* out_len,
+                             uint32_t* err, bool wide) {
   if (!c || !vectors || !verts || !offs || !lens || (!ids && nids) || !out || !out_len || !err)
     return fail(PM_EINVAL, "NULL argument");
+  if (wide && !wide_dim_ok(dim)) return fail(PM_EINVAL, kWideDimText);
   if (m == 0 || m > pmk::prune_max_m()) return fail(PM_EINVAL, "m must be in [1, 64]");
-  if (dim == 0 || dim > pmk::prune_max_dim()) return fail(PM_EINVAL, "dim must be in [1, 256]");
+  if (!wide && (dim == 0 || dim > pmk::prune_max_dim())) return fail(PM_EINVAL, "dim must be in [1, 256]");
   if (n == 0 || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be in [1, 2^32-1)");
   if (nverts == 0 || nverts > n) return fail(PM_EINVAL, "nverts must be in [1, n]");
   for (uint64_t i = 0; i < nids; ++i)
@@ -439,11 +482,25 @@ extern "C" int pm_robust_prune(pm_ctx* c, const float* vectors, uint64_t n, uint
   const std::vector<uint32_t> vs(verts, verts + nverts), none, conn(ids, ids + nids);
   std::vector<uint32_t> P, PL;
   CHK(prune_lists(c, X.as<float>(), n, (uint32_t)dim, presorted ? none : vs, presorted ? vs : none, coff, clen, conn, m,
-                  alpha, P, PL, err));
+                  alpha, P, PL, err, wide));
   for (uint64_t b = 0; b < nverts; ++b) {
     const uint32_t u = verts[b];
     out_len[b] = PL[u];
     memcpy(out + b * m, &P[(uint64_t)u * m], (size_t)std::min<uint32_t>(PL[u], m) * 4);
   }
   return 0;
+}
+extern "C" int pm_robust_prune(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* verts,
+                               uint64_t nverts, const uint64_t* offs, const uint32_t* lens, const uint32_t* ids,
+                               uint64_t nids, uint32_t m, float alpha, int presorted, uint32_t* out,
+                               uint32_t* out_len, uint32_t* err) {
+  return robust_prune_impl(c, vectors, n, dim, verts, nverts, offs, lens, ids, nids, m, alpha, presorted, out, out_len,
+                           err, false);
+}
+extern "C" int pm_robust_prune_wide(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* verts,
+                                    uint64_t nverts, const uint64_t* offs, const uint32_t* lens, const uint32_t* ids,
+                                    uint64_t nids, uint32_t m, float alpha, int presorted, uint32_t* out,
+                                    uint32_t* out_len, uint32_t* err) {
+  return robust_prune_impl(c, vectors, n, dim, verts, nverts, offs, lens, ids, nids, m, alpha, presorted, out, out_len,
+                           err, true);
 }

@@ -35,17 +35,12 @@
 #include <hip/hip_runtime.h>
 
 #include "pm_internal.h"
+#include "pm_graph_dev.h"
 
 namespace pm {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kKnnRows = 64;      // query rows per workgroup
 constexpr int kKnnCols = 128;     // base rows per tile
-constexpr int kKnnTop = 64;       // prefilter keys kept per query row
 constexpr int kKnnThreads = 512;  // 8 waves: 2 row blocks x 4 column blocks of 32x32
-constexpr uint64_t kNoKey = ~0ull;
 constexpr int kKnnMaxDim = 192;   // the widest row knn_pad_dim() accepts
 
 // rows [n][dim] f32 -> out [n][dp] bf16 (zero padded), norms [n] = sum of the
@@ -107,31 +102,6 @@ struct KnnLds {
   uint32_t any[2];
   __bf16 b[kKnnCols][DP + 8];               // padded rows: conflict-free 16-B fragment reads
 };
-
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t v, int d) {
-  const uint32_t lo = __shfl_up((uint32_t)v, d), hi = __shfl_up((uint32_t)(v >> 32), d);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
-  return ((uint64_t)__builtin_amdgcn_readlane((uint32_t)(v >> 32), l) << 32) |
-         __builtin_amdgcn_readlane((uint32_t)v, l);
-}
-
-// Insert the wave-uniform key x into the sorted top-64 t (lane i holds entry i).
-__device__ __forceinline__ uint64_t knn_insert(uint64_t t, uint64_t x, uint32_t lane) {
-  if (x >= readlane64(t, 63)) return t;   // uniform: x and the last key are wave-uniform
-  const uint32_t pos = __popcll(__ballot(t < x));
-  const uint64_t up = shfl_up64(t, 1);
-  return lane < pos ? t : (lane == pos ? x : up);
-}
-
-// Merge the row's insertion buffer into its sorted top-64 (lane i holds entry i).
-__device__ __forceinline__ void knn_merge_row(uint64_t* top, const uint64_t* buf, uint32_t n, uint32_t lane) {
-  uint64_t t = top[lane];
-  for (uint32_t e = 0; e < n; ++e) t = knn_insert(t, buf[e], lane);
-  top[lane] = t;
-}
 
 template <int DP>
 __global__ void __launch_bounds__(kKnnThreads) k_knn_bf16(const __bf16* __restrict__ X, const float* __restrict__ xn,
@@ -413,77 +383,6 @@ __global__ void __launch_bounds__(kKnn3Threads) k_knn_bf16x3(const __bf16* __res
   }
 }
 
-// 8-lane L2Dist of a (global f32) and b (global f32) in the reference order;
-// every lane of the group returns the distance.
-__device__ __forceinline__ float l2_group8(const float* __restrict__ a, const float* __restrict__ b, uint32_t dim,
-                                           uint32_t k) {
-  const uint32_t dimS = dim & ~7u;
-  float acc = 0.0f;
-  for (uint32_t t = k; t < dimS; t += 8) {
-    const float d = __fsub_rn(a[t], b[t]);
-    acc = __fadd_rn(acc, __fmul_rn(d, d));
-  }
-  acc = __fadd_rn(acc, __shfl_xor(acc, 1));
-  acc = __fadd_rn(acc, __shfl_xor(acc, 2));
-  acc = __fadd_rn(acc, __shfl_xor(acc, 4));
-  float d = dimS ? acc : 0.0f;
-  for (uint32_t i = dimS; i < dim; ++i) {   // build_graph.go:122-125 scalar tail
-    const float t = __fsub_rn(a[i], b[i]);
-    d = __fadd_rn(d, __fmul_rn(t, t));
-  }
-  return d;
-}
-
-// Bitonic sort of 64 u64 keys held one per lane (ascending by lane).
-__device__ __forceinline__ uint64_t wave_sort64(uint64_t x, uint32_t lane) {
-  for (int k = 2; k <= 64; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const uint32_t lo = __shfl_xor((uint32_t)x, j), hi = __shfl_xor((uint32_t)(x >> 32), j);
-      const uint64_t y = ((uint64_t)hi << 32) | lo;
-      const bool up = (lane & k) == 0, lower = (lane & j) == 0;
-      const uint64_t mn = x < y ? x : y, mx = x < y ? y : x;
-      x = (up == lower) ? mn : mx;
-    }
-  }
-  return x;
-}
-
-// One wave's re-rank of a query row: exact L2Dist of the 64 candidates, keys
-// (dist, id) in the wave's LDS row, sorted; lane i returns the i-th key.
-__device__ __forceinline__ uint64_t knn_rerank_keys(const float* __restrict__ X, uint64_t N, uint32_t dim,
-                                                    const float* __restrict__ q, const uint32_t* __restrict__ cand,
-                                                    uint64_t* keys, uint32_t lane) {
-  const uint32_t g = lane >> 3, k = lane & 7;
-  for (uint32_t r = 0; r < 8; ++r) {
-    const uint32_t c = r * 8 + g;
-    const uint32_t id = cand[c];
-    const bool ok = id < N;
-    const float d = l2_group8(X + (ok ? (uint64_t)id : 0) * dim, q, dim, k);
-    if (k == 0) keys[c] = ok ? (((uint64_t)__float_as_uint(d) << 32) | id) : kNoKey;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // this wave's LDS keys visible to its lanes
-  __builtin_amdgcn_wave_barrier();
-  return wave_sort64(keys[lane], lane);
-}
-
-// The first K of a row's sorted keys x (self dropped when self_base: the
-// reference removes u from NGT's K results) go to out[row][K], their count to
-// len[row].
-__device__ __forceinline__ void knn_emit(uint64_t x, uint64_t row, uint32_t K, int self_base, uint32_t lane,
-                                         uint32_t* __restrict__ out, float* __restrict__ dist_out,
-                                         uint32_t* __restrict__ len) {
-  const uint32_t id = (uint32_t)x;
-  const bool in = lane < K && x != kNoKey;
-  const bool self = self_base && id == (uint32_t)row;
-  const uint64_t keep = __ballot(in && !self);
-  const uint32_t pos = __popcll(keep & ((1ull << lane) - 1));
-  if (in && !self) {
-    out[row * K + pos] = id;
-    if (dist_out) dist_out[row * K + pos] = __uint_as_float((uint32_t)(x >> 32));
-  }
-  if (lane == 0) len[row] = __popcll(keep);
-}
-
 // One wave per query row: exact L2Dist of the 64 candidates, keys (dist, id),
 // sorted; the first K (self dropped when self_base) go to out[row][K], their
 // count to len[row].
@@ -499,12 +398,6 @@ __global__ void __launch_bounds__(kBlock) k_knn_rerank(const float* __restrict__
   const uint64_t x = knn_rerank_keys(X, N, dim, Q + row * dim, cand + row * kKnnTop, keys[w], lane);
   knn_emit(x, row, K, self_base, lane, out, dist_out, len);
 }
-
-// Bounds of the certificate: eps = crel (qn + maxnorm) +
-// kCertAbs bounds |prefilter distance - L2Dist| of k_knn_bf16x3 for every base
-// row while qn + maxnorm <= kCertMaxSum (no overflow in the products or sums).
-constexpr float kCertAbs = 0x1.0p-50f;
-constexpr float kCertMaxSum = 0x1.0p126f;
 
 // k_knn_rerank with the certificate of pm_knn_exact.  The row's result is the
 // brute-force one if N <= 64 (every base row is a candidate) or if the K-th

@@ -527,4 +527,19 @@ void prune(hipStream_t st, const float* X, uint32_t dim, const uint32_t* verts, 
 // L2Dist of every candidate of the listed vertices (hub lists above prune_max_list())
 void cand_dist(hipStream_t st, const float* X, uint32_t dim, const uint32_t* verts, uint64_t nverts,
                const uint64_t* offs, const uint32_t* lens, const uint32_t* ids, float* dist_g);
+// rows of 193 to 1,024 dimensions (pm_graph_wide.hip; pm_knn_wide, pm_build_graph_wide): the padded
+// width (the next multiple of 64; 0 for dim 0 or above 1,024), the K-chunked three-product
+// prefilter at that width, and the brute-force and robustPrune kernels with one row in LDS.
+// Arguments as knn_prefilter_x3, knn_brute and prune; to_bf16x2, knn_rerank_cert and cand_dist
+// take any width.
+uint32_t knn_pad_dim_wide(uint32_t dim);
+void knn_prefilter_x3_w(hipStream_t st, const void* Xh, const void* Xl, const float* xn, uint64_t N, const void* Qh,
+                        const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau,
+                        uint32_t* out_hi = nullptr);
+void knn_brute_w(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, const uint64_t* list,
+                 uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
+void prune_w(hipStream_t st, const float* X, uint32_t dim, const uint32_t* verts, uint64_t nverts,
+             const uint64_t* offs, uint64_t stride, const uint32_t* lens, const uint32_t* ids, uint32_t m,
+             float alpha, uint32_t* out, uint32_t* out_len, uint32_t* err, const uint32_t* sorted_pos = nullptr,
+             const float* dist_g = nullptr);
 }  // namespace pmk
