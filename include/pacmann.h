@@ -109,6 +109,14 @@ int pm_timing_enable(pm_ctx* ctx, int level);
  * is created; its clients and sessions share the image and the decision.
  * "host_fold_rot512p" counts the folds over a packed image, "host_fold_rot512"
  * those over a plain one.
+ * "answer_pack": whether such a graph DB (zero low halves in every coordinate
+ * word, E % 4 == 0, E <= 256 words, dim % 8 == 0) also gets a packed row image
+ * (rows of 2 dim + 4 (2E - dim) bytes: the coordinates' high halves, then the
+ * other words whole) which the pair answer kernels of shared steps gather
+ * instead of the DB's rows (1), or not (0); -1: PM_ANSWER_PACK (default on); any
+ * other value is PM_EINVAL.  Read when a server is created; its clients and
+ * sessions share the image and the decision.  "host_answer_packed" counts the
+ * "host_path_answer_p5" / "host_path_answer_p" launches that gathered it.
  * "device_loop": the batched serving loop on the device (1 / 0; -1 automatic).
  * "fault_drl_query" (tests): the device loop fails before queueing query
  * `value` (-1 off); its sessions are then unusable (every later call on them

@@ -156,6 +156,11 @@ extern "C" int pm_set_option(const char* name, int value) {
     pmk::set_fold_pack(value);
     return 0;
   }
+  if (!strcmp(name, "answer_pack")) {
+    if (value < -1 || value > 1) return fail(PM_EINVAL, "answer_pack takes 1, 0 or -1");
+    pmk::set_answer_pack(value);
+    return 0;
+  }
   if (pmk::set_option(name, value)) return fail(PM_EINVAL, std::string("unknown option ") + name);
   return 0;
 }

@@ -248,7 +248,7 @@ static int drl_step(DrlTeam& T, const DrlShape& sh) {
   S.subs_h = S.subs;   // the descriptor is on the device already
   S.sb_h = S.sb;
   S.done = G.done.as<uint32_t>();
-  S.db = e0->db->as<uint64_t>();
+  e0->step_db(S);
   S.q = nullptr;   // each partition's PmPart::qv
   step_out(S, T.out.p, T.nsub);
   S.E = G.E; S.dim = G.dim; S.nsub = T.nsub; S.np = T.S * G.Pl;

@@ -146,17 +146,22 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
   // all have zero low halves, e.g. f32 holding SIFT's bytes, gets the packed
   // image (FOLD_ROT512P): one reduction over the rows decides, once, since the
   // DB does not change.  A client takes its server's image and decision.
+  // The same property lets the pair answer gather packed rows (the row image
+  // below), so the reduction runs once if either image wants it.
   uint64_t off_img = 0;
-  if (!g->owned_list.empty() && pmk::fold_image_ok(g->minCS, g->maxCS, (uint32_t)g->E)) {
-    if (server) {
-      g->img_npk = server->img_npk;
-    } else if (const uint32_t npk = pmk::fold_pack_slices(g->minCS, g->maxCS, (uint32_t)g->E, coord_words)) {
-      DevBuf flag;
-      CHK(flag.reserve(64));
-      if (pmk::coord_low_zero(ctx->stream, g->db->as<uint64_t>(), off_db, (uint32_t)g->E, coord_words, flag.as<uint32_t>()))
-        g->img_npk = npk;
-      HIPCHK(hipGetLastError());
-    }
+  const bool fold_img = !g->owned_list.empty() && pmk::fold_image_ok(g->minCS, g->maxCS, (uint32_t)g->E);
+  const uint32_t want_npk = !server && fold_img ? pmk::fold_pack_slices(g->minCS, g->maxCS, (uint32_t)g->E, coord_words) : 0;
+  const uint32_t want_apk = !server && !g->owned_list.empty() ? pmk::answer_pack_segs((uint32_t)g->E, coord_words) : 0;
+  bool low_zero = false;
+  if (want_npk || want_apk) {
+    DevBuf flag;
+    CHK(flag.reserve(64));
+    low_zero = pmk::coord_low_zero(ctx->stream, g->db->as<uint64_t>(), off_db, (uint32_t)g->E, coord_words, flag.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+  }
+  if (fold_img) {
+    if (server) g->img_npk = server->img_npk;
+    else if (low_zero) g->img_npk = want_npk;
     for (uint32_t i : g->owned_list) {
       PmPart& d = g->parts[i].d;
       d.img = (const uint64_t*)(uintptr_t)off_img;
@@ -184,6 +189,23 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
       }
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+  }
+  // the packed row image of the pair answer (k_answer_p5k / k_answer_pk): the
+  // owned rows in db's order, without the coordinates' zero low halves.  Built
+  // once by the server under the fold image's memory rule; db stays for every
+  // other reader.  A client takes its server's image and decision.
+  if (server) {
+    g->apk = server->apk; g->apk_nseg = server->apk_nseg; g->apk_cseg = server->apk_cseg;
+  } else if (want_apk && low_zero) {
+    const uint64_t bytes = off_db * want_apk * 16;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes <= free_b / 4) {
+      CHK(g->apk->reserve(bytes));
+      pmk::answer_pack_image(ctx->stream, g->apk->as<uint64_t>(), g->db->as<uint64_t>(), off_db, (uint32_t)g->E, coord_words);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      g->apk_nseg = want_apk; g->apk_cseg = coord_words / 8;
     }
   }
   CHK(g->tag.reserve(off_tag * 4));
@@ -724,6 +746,7 @@ int step_chain(pm_ctx* c, StepBufs& B, PmStep& S, const pmk::StepShape& shape, u
     if (form < 0) return;
     c->timed_ext(name, bytes, [&](pmk::PmEvents ev) { pmk::step_launch(st, S, plan, stage, ev); }, 2);
     c->host_add(pm_ctx::step_counter(stage, form), stage == pmk::STAGE_FUSED ? plan.nhelp : 0.0);   // k_step: its nhelp
+    if (pmk::step_answer_packed(S, plan, stage)) c->host_add(HT_ANSWER_PACKED, 0.0);
   };
 #ifdef PM_STEP_STAMPS
   LaunchStamps ss;   // {grid, nsub, cblk, np} + grid x 8 stamps per k_step (PM_STAMP_FILE)
@@ -796,7 +819,7 @@ int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
   HIPCHK(hipMemsetAsync(B.stamps.p, 0, g->P * 64 * 8, st));
   S.stamps = B.stamps.as<uint64_t>();
 #endif
-  S.db = g->db->as<uint64_t>();
+  g->step_db(S);
   S.q = q_dev;
   step_out(S, B.out_h.p, nsub);
   S.E = (uint32_t)E; S.dim = q_dev ? dim : 0; S.nsub = nsub; S.np = (uint32_t)g->P;

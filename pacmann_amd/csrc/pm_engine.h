@@ -219,6 +219,15 @@ struct Engine {
   std::shared_ptr<DevBuf> db = std::make_shared<DevBuf>();   // server DB; shared by the clients of pm_batchpir_create_client
   std::shared_ptr<DevBuf> img = std::make_shared<DevBuf>();  // the DB's fold image (pmk::fold_image), shared likewise
   uint32_t img_npk = 0;   // its packed coordinate slices (FOLD_ROT512P; 0: a plain image), the server's for a client
+  // the DB's packed row image for the pair answer (pmk::answer_pack_image), shared likewise; its 16-B segments
+  // per row (0: no image) and how many of them are coordinates.  step_db puts them into a step.
+  std::shared_ptr<DevBuf> apk = std::make_shared<DevBuf>();
+  uint32_t apk_nseg = 0, apk_cseg = 0;
+  void step_db(PmStep& S) const {
+    S.db = db->as<uint64_t>();
+    S.dbp = apk_nseg ? apk->as<uint64_t>() : nullptr;
+    S.pk_nseg = apk_nseg; S.pk_cseg = apk_cseg;
+  }
   DevBuf zero16, parts_d, owned_d, tag, pp, parity, ridx, rval, hist, fqn, arena, tab, tabT, cur, done, gran;
   HostBuf parts_stage;   // pinned copy of [parts | owned parts] for the asynchronous upload (upload_parts_async)
   hipEvent_t stage_ev = nullptr;   // the last upload from parts_stage (the stage is rewritten only after it)

@@ -245,7 +245,7 @@ static int group_step(StepGroup& G, const std::vector<char>& in) {
   }
   S.done = G.done.as<uint32_t>();
   Engine* e0 = G.es[0];
-  S.db = e0->db->as<uint64_t>();
+  e0->step_db(S);
   S.q = nullptr;   // each partition's PmPart::qv
   if (G.comb) {   // sharded: results stay on the device for group_exchange's records
     CHK(G.out_d.reserve(step_out_bytes(nsub, G.E)));

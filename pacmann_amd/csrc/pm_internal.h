@@ -220,6 +220,11 @@ struct PmStep {
                                // [2] chained sub-queries, [3..] their list (filled by the
                                // resolvers; re-armed by each step's finisher)
   const PM_G uint64_t* db;
+  // The server's packed row image for k_answer_p5k / k_answer_pk (pmk::answer_pack_image; null: none):
+  // row r = the high halves of db row r's 8 pk_cseg coordinate words as half-words, then its other
+  // 32-bit words whole; pk_nseg 16-B segments per row, the first pk_cseg of them coordinates
+  const PM_G uint64_t* dbp;
+  uint32_t pk_nseg, pk_cseg;
   const PM_G float* q;         // search query (device) or null
   PM_G PmOutHdr* hdr_h;        // pinned host outputs
   PM_G uint64_t* rows_h;
@@ -376,6 +381,20 @@ void set_fold_pack(int v);
 uint32_t fold_pack_shape(uint32_t E, uint32_t dim);
 uint32_t fold_pack_slices(uint32_t minCS, uint32_t maxCS, uint32_t E, uint32_t dim);
 bool coord_low_zero(hipStream_t st, const uint64_t* rows, uint64_t nrows, uint32_t E, uint32_t dim, uint32_t* flag);
+// The answer's packed row image (k_answer_p5k / k_answer_pk): for the same kind of
+// DB, a row-major copy of the rows without the coordinates' low halves: row r =
+// the high halves of its `dim` coordinate words as consecutive half-words, then
+// its 2E - dim other 32-bit words whole (2 dim + 4 (2E - dim) bytes; SIFT1M: 384
+// instead of 640).  answer_pack_shape: the row's 16-B segments, 0 where the
+// entries do not qualify (a graph DB, E % 4 == 0 so that the gather's E & ~3 rule
+// cuts nothing, E <= 256, dim % 8 == 0: whole segments of eight half-words, and
+// then a stride of whole segments).  answer_pack_segs: the same for a server
+// being created, 0 also unless "answer_pack" / PM_ANSWER_PACK (1 / 0, -1 the
+// environment's, default on) allows it; read there and nowhere later.
+void set_answer_pack(int v);
+uint32_t answer_pack_shape(uint32_t E, uint32_t dim);
+uint32_t answer_pack_segs(uint32_t E, uint32_t dim);
+void answer_pack_image(hipStream_t st, uint64_t* img, const uint64_t* rows, uint64_t nrows, uint32_t E, uint32_t dim);
 // k_fold_image's index map on the host (pm_fold_image_map): for image items
 // [x0, x0 + n) of a partition, the row, its first 32-bit word and whether the
 // item packs the high halves of 8 words (else it holds 4 whole words)
@@ -440,6 +459,12 @@ struct StepPlan {
 StepPlan step_plan(const StepShape& s, const StepOpts& O);
 // Issues one launch of a plan (S as the plan says: pmh::step_chain).
 void step_launch(hipStream_t st, const PmStep& S, const StepPlan& plan, int stage, PmEvents ev = {});
+// whether step_launch takes the packed instance at `stage`: the pair answer (k_answer_p5 / k_answer_p) of a
+// step whose server has the packed row image (PmStep::dbp); counted in "host_answer_packed"
+inline bool step_answer_packed(const PmStep& S, const StepPlan& plan, int stage) {
+  const int form = plan.at[stage].form;
+  return stage == STAGE_ANSWER && (form == FORM_ANSWER_P5 || form == FORM_ANSWER_P) && S.dbp != nullptr;
+}
 uint32_t step_max_sub_per_part();
 uint32_t step_max_ss();
 uint32_t step_max_e();

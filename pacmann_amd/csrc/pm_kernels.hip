@@ -777,6 +777,28 @@ __global__ void __launch_bounds__(kBlock) k_fold_image(uint4* __restrict__ img, 
     img[x] = v;
   }
 }
+// The answer's packed row image (pmk::answer_pack_image): item x = 16-B segment
+// x % nseg of row x / nseg.  The first cseg segments hold the high halves of
+// eight coordinate words each (the packing of k_fold_image), the others four
+// whole words from 32-bit word 8 cseg on.
+__global__ void __launch_bounds__(kBlock) k_answer_pack_image(uint4* __restrict__ img, const uint64_t* __restrict__ rows,
+                                                             uint64_t nitems, uint32_t E, uint32_t nseg, uint32_t cseg) {
+  for (uint64_t x = (uint64_t)blockIdx.x * kBlock + threadIdx.x; x < nitems; x += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t r = x / nseg;
+    const uint32_t s = (uint32_t)(x - r * nseg);
+    const uint32_t* const row = reinterpret_cast<const uint32_t*>(rows + r * E);
+    uint4 v;
+    if (s < cseg) {
+      const uint4* const p = reinterpret_cast<const uint4*>(row + 8 * s);
+      const uint4 a = p[0], u = p[1];
+      v = make_uint4((a.x >> 16) | (a.y & 0xffff0000u), (a.z >> 16) | (a.w & 0xffff0000u),
+                     (u.x >> 16) | (u.y & 0xffff0000u), (u.z >> 16) | (u.w & 0xffff0000u));
+    } else {
+      v = *reinterpret_cast<const uint4*>(row + 8 * cseg + 4 * (s - cseg));
+    }
+    img[x] = v;
+  }
+}
 // OR of the low halves of the coordinate words (32-bit words [0, dim) of every
 // E-word row; dim % 4 == 0, E even): *out becomes non-zero if any is non-zero
 __global__ void __launch_bounds__(kBlock) k_coord_low_or(const uint64_t* __restrict__ rows, uint64_t nrows, uint32_t E,
@@ -1142,6 +1164,27 @@ uint32_t fold_pack_slices(uint32_t minCS, uint32_t maxCS, uint32_t E, uint32_t d
 }
 uint32_t fold_pack_shape(uint32_t E, uint32_t dim) {
   return dim && dim % 16 == 0 && dim / 8 <= E / 4 ? dim / 16 : 0;
+}
+static std::atomic<int> g_answer_pack{-1};
+void set_answer_pack(int v) { g_answer_pack.store(v < 0 ? -1 : (v ? 1 : 0)); }
+uint32_t answer_pack_shape(uint32_t E, uint32_t dim) {
+  if (!dim || E % 4 || E > 256 || dim % 8 || dim >= 2 * E) return 0;
+  const uint32_t stride = 2 * dim + 4 * (2 * E - dim);   // bytes
+  return stride % 16 ? 0 : stride / 16;
+}
+// "answer_pack" (else PM_ANSWER_PACK, default on) is read here only, while a
+// server is created; its clients share the image and so the decision.
+uint32_t answer_pack_segs(uint32_t E, uint32_t dim) {
+  static const bool env = [] { const char* e = getenv("PM_ANSWER_PACK"); return !e || e[0] != '0'; }();
+  const int v = g_answer_pack.load();
+  return (v < 0 ? env : v == 1) ? answer_pack_shape(E, dim) : 0;
+}
+void answer_pack_image(hipStream_t st, uint64_t* img, const uint64_t* rows, uint64_t nrows, uint32_t E, uint32_t dim) {
+  const uint32_t nseg = answer_pack_shape(E, dim);
+  const uint64_t nitems = nrows * nseg;
+  unsigned grid = cdiv(nitems, kBlock);
+  if (grid > 256 * 32) grid = 256 * 32;
+  if (grid) hipLaunchKernelGGL(k_answer_pack_image, dim3(grid), dim3(kBlock), 0, st, (uint4*)img, rows, nitems, E, nseg, dim / 8);
 }
 bool coord_low_zero(hipStream_t st, const uint64_t* rows, uint64_t nrows, uint32_t E, uint32_t dim, uint32_t* flag) {
   if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return false;

@@ -2284,14 +2284,22 @@ __device__ __forceinline__ void ansp_set(const PmStep& S, const AnsQ& a, uint4 q
     for (uint32_t i = tid; i < P.SS; i += blockDim.x) qo[i] = (uint16_t)(hash4(P.seed, DOM_DUMMY, P.idx, a.idx, i) & mask);
   }
 }
-template <int W, int NT, int KG>
+// PK: the rows come from the server's packed row image (PmStep::dbp): pk_nseg
+// 16-B segments per row instead of (E & ~3) / 2, the first pk_cseg of them the
+// high halves of eight coordinate words each.  The XOR of half-words is the
+// high half of the words' XOR, so only reduce differs: it expands a coordinate
+// segment to its eight words (low halves zero) and L.row is what the plain
+// gather leaves.  W == 2.
+template <int W, int NT, int KG, bool PK>
 struct AnsGather {   // one thread's share of a sub-query's XOR gather (HOT LOOP E)
   typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+  static_assert(!PK || W == 2, "packed rows are gathered in 16-B segments");
   uint32_t seg, sl, nsl;
   uint64_t a0 = 0, a1 = 0;
   u64x2 x[KG];
-  __device__ __forceinline__ void init(uint32_t E) {
-    const uint32_t NSEG = (E & ~3u) / W;   // <= NT at the shapes this kernel serves (E <= kSmallE, W 2)
+  __device__ __forceinline__ uint32_t nseg(const PmStep& S) const { return PK ? S.pk_nseg : (S.E & ~3u) / W; }
+  __device__ __forceinline__ void init(const PmStep& S) {
+    const uint32_t NSEG = nseg(S);   // <= NT at the shapes this kernel serves (E <= kSmallE, W 2)
     nsl = NT / NSEG;
     sl = threadIdx.x / NSEG;
     seg = threadIdx.x % NSEG;
@@ -2307,12 +2315,13 @@ struct AnsGather {   // one thread's share of a sub-query's XOR gather (HOT LOOP
       const uint32_t i = i0 + u * nsl;
       rr[u] = (sl < nsl && i < P.SS) ? i * P.CS + rr[u] : ~0u;
     }
-    const PM_G uint64_t* base = S.db + P.row0 * S.E;
+    const uint32_t stride = PK ? S.pk_nseg * 2 : S.E;   // words per row
+    const PM_G uint64_t* base = (PK ? S.dbp : S.db) + P.row0 * stride;
 #pragma unroll
     for (int u = 0; u < KG; ++u) {
       x[u] = u64x2{0, 0};
       if (rr[u] < P.N) {
-        const PM_G uint64_t* q = base + (uint64_t)rr[u] * S.E + (uint64_t)seg * W;
+        const PM_G uint64_t* q = base + (uint64_t)rr[u] * stride + (uint64_t)seg * W;
 #if PM_ANSWER_NTLOAD
         if (W == 2) x[u] = __builtin_nontemporal_load(reinterpret_cast<const PM_G u64x2*>(q));
         else x[u].x = __builtin_nontemporal_load(q);
@@ -2330,8 +2339,8 @@ struct AnsGather {   // one thread's share of a sub-query's XOR gather (HOT LOOP
   __device__ __forceinline__ uint32_t batches(const PmPart& P) const { return (P.SS + KG * nsl - 1) / (KG * nsl); }
   // the slices' partial XORs -> row.w[0 .. E & ~3)
   template <class LDS>
-  __device__ __forceinline__ void reduce(LDS& L, uint32_t E) {
-    const uint32_t tid = threadIdx.x, NSEG = (E & ~3u) / W;
+  __device__ __forceinline__ void reduce(LDS& L, const PmStep& S) {
+    const uint32_t tid = threadIdx.x, NSEG = nseg(S);
     L.red[tid * 2] = a0;
     L.red[tid * 2 + 1] = a1;
     __syncthreads();
@@ -2341,8 +2350,16 @@ struct AnsGather {   // one thread's share of a sub-query's XOR gather (HOT LOOP
         x0 ^= L.red[(k * NSEG + tid) * 2];
         x1 ^= L.red[(k * NSEG + tid) * 2 + 1];
       }
-      L.row.w[tid * W] = x0;
-      if (W == 2) L.row.w[tid * W + 1] = x1;
+      if (PK && tid < S.pk_cseg) {   // half-words h0 .. h7 -> coordinate words 8 tid .. 8 tid + 7 = h << 16
+        L.row.w[tid * 4] = ((x0 & 0xffffull) << 16) | ((x0 & 0xffff0000ull) << 32);
+        L.row.w[tid * 4 + 1] = ((x0 >> 16) & 0xffff0000ull) | (x0 & 0xffff000000000000ull);
+        L.row.w[tid * 4 + 2] = ((x1 & 0xffffull) << 16) | ((x1 & 0xffff0000ull) << 32);
+        L.row.w[tid * 4 + 3] = ((x1 >> 16) & 0xffff0000ull) | (x1 & 0xffff000000000000ull);
+      } else {
+        const uint32_t w = PK ? S.pk_cseg * 4 + (tid - S.pk_cseg) * 2 : tid * W;   // the id words follow whole
+        L.row.w[w] = x0;
+        if (W == 2) L.row.w[w + 1] = x1;
+      }
     }
     __syncthreads();
   }
@@ -2455,9 +2472,9 @@ __device__ __forceinline__ bool ansp_gathers(const AnsQ& a) {
 // the next one's first row batch is issued before slot c's reduction, decode
 // and publication, and slot c is refilled (record + query set of s_{k+2})
 // while that batch is in flight.
-template <int W, int NT, int KG, int C>
+template <int W, int NT, int KG, bool PK, int C>
 __device__ __forceinline__ bool ansp_turn(const PmStep& S, AnswerPLds<NT>& L, AnsQ (&q)[2], uint4 (&qpv)[2],
-                                          AnsGather<W, NT, KG> (&g)[2], uint32_t k, bool first) {
+                                          AnsGather<W, NT, KG, PK> (&g)[2], uint32_t k, bool first) {
   constexpr int N = C ^ 1;
   const uint32_t ns = S.nsub, G = gridDim.x;
   const bool hasN = blockIdx.x + (k + 1) * G < ns;
@@ -2476,7 +2493,7 @@ __device__ __forceinline__ bool ansp_turn(const PmStep& S, AnswerPLds<NT>& L, An
     g[N].a0 = g[N].a1 = 0;
     g[N].load(S, S.parts[q[N].part], L.qo[N], 0);
   }
-  if (ansp_gathers(q[C])) g[C].reduce(L, S.E);
+  if (ansp_gathers(q[C])) g[C].reduce(L, S);
   ansp_epilogue<W, NT>(S, q[C], L);   // ends with a barrier: L.qo[C] is free
   if (!hasN) return false;
   if (blockIdx.x + (k + 2) * G < ns) {
@@ -2496,7 +2513,7 @@ __device__ __forceinline__ bool ansp_turn(const PmStep& S, AnswerPLds<NT>& L, An
 #define PM_ANSWER_P_WAVES 6   // min waves per SIMD: <= 80 VGPRs (the next sub-query's row batch stays live through
                               // an epilogue); 12 two-wave workgroups per CU = the 3,072 of a 6,144-sub-query step
 #endif
-template <int W, int NT, int KG>
+template <int W, int NT, int KG, bool PK = false>
 __device__ __forceinline__ void answer_p_body(const PmStep& S, AnswerPLds<NT>& L) {
   AnsQ q[2];
   uint4 qpv[2];
@@ -2511,16 +2528,16 @@ __device__ __forceinline__ void answer_p_body(const PmStep& S, AnswerPLds<NT>& L
   ansp_set(S, q[0], qpv[0], L.qo[0]);
   if (has1) ansp_set(S, q[1], qpv[1], L.qo[1]);
   __syncthreads();
-  AnsGather<W, NT, KG> g[2];
-  g[0].init(S.E);
-  g[1].init(S.E);
+  AnsGather<W, NT, KG, PK> g[2];
+  g[0].init(S);
+  g[1].init(S);
   // straight-line turns (a loop keeps every slot's state live across its
   // back edge and spills): at most PM_ANSWER_PK_MAX sub-queries per workgroup
   static_assert(PM_ANSWER_PK_MAX >= 2 && PM_ANSWER_PK_MAX <= 4, "k_answer_p turns");
-  if (!ansp_turn<W, NT, KG, 0>(S, L, q, qpv, g, 0, true)) return;
-  if (!ansp_turn<W, NT, KG, 1>(S, L, q, qpv, g, 1, false)) return;
-  if (PM_ANSWER_PK_MAX > 2 && !ansp_turn<W, NT, KG, 0>(S, L, q, qpv, g, 2, false)) return;
-  if (PM_ANSWER_PK_MAX > 3) ansp_turn<W, NT, KG, 1>(S, L, q, qpv, g, 3, false);
+  if (!ansp_turn<W, NT, KG, PK, 0>(S, L, q, qpv, g, 0, true)) return;
+  if (!ansp_turn<W, NT, KG, PK, 1>(S, L, q, qpv, g, 1, false)) return;
+  if (PM_ANSWER_PK_MAX > 2 && !ansp_turn<W, NT, KG, PK, 0>(S, L, q, qpv, g, 2, false)) return;
+  if (PM_ANSWER_PK_MAX > 3) ansp_turn<W, NT, KG, PK, 1>(S, L, q, qpv, g, 3, false);
 }
 template <int W, int NT>
 __global__ void __launch_bounds__(NT, PM_ANSWER_P_WAVES) k_answer_p(PmStep S) {
@@ -2537,6 +2554,26 @@ template <int W, int NT>
 __global__ void __launch_bounds__(NT, 5) __attribute__((amdgpu_num_vgpr(88))) k_answer_p5(PmStep S) {
   __shared__ AnswerPLds<NT> L;
   answer_p_body<W, NT, kAnsP5KG>(S, L);
+}
+// The packed instances (AnsGather's PK): the same two kernels over the server's
+// packed row image, within the same register budgets (88 / 80 VGPRs, no
+// scratch).  SIFT1M's 384-B rows are 24 segments, so a workgroup has 5 slices of
+// rows instead of 3 and SetSize 124 gives a thread 25 (one slice 24) rows.
+#ifndef PM_ANSWER_PK5_KG
+#define PM_ANSWER_PK5_KG 9   // rows per batch of k_answer_p5k: 3 batches of 45 rows (85 VGPRs); 5 / 7 / 8 rows
+#endif                       // (69 / 77 / 81 VGPRs; 5, 4, 4 batches) measured no better
+#ifndef PM_ANSWER_PK_KG
+#define PM_ANSWER_PK_KG 6    // ... of k_answer_pk: 5 batches of 30 (73 VGPRs); 7 / 8 rows (75 / 79) no better
+#endif
+template <int W, int NT>
+__global__ void __launch_bounds__(NT, PM_ANSWER_P_WAVES) k_answer_pk(PmStep S) {
+  __shared__ AnswerPLds<NT> L;
+  answer_p_body<W, NT, PM_ANSWER_PK_KG, true>(S, L);
+}
+template <int W, int NT>
+__global__ void __launch_bounds__(NT, 5) __attribute__((amdgpu_num_vgpr(88))) k_answer_p5k(PmStep S) {
+  __shared__ AnswerPLds<NT> L;
+  answer_p_body<W, NT, PM_ANSWER_PK5_KG, true>(S, L);
 }
 
 // ---- k_gather: the server's XOR gather of wide sets, split ----------------
@@ -2905,8 +2942,14 @@ void step_launch(hipStream_t st, const PmStep& S, const StepPlan& plan, int stag
     case FORM_MR_S4: PM_LAUNCH((k_match_resolve_s<4, 256>)); break;
     case FORM_MR_GENERAL: PM_LAUNCH(k_match_resolve<kMatchHints / kBlock>); break;
     case FORM_GATHER: PM_LAUNCH_W(k_gather); break;
-    case FORM_ANSWER_P5: PM_LAUNCH((k_answer_p5<2, kAnsPNT>)); break;
-    case FORM_ANSWER_P: PM_LAUNCH((k_answer_p<2, kAnsPNT>)); break;
+    case FORM_ANSWER_P5:
+      if (step_answer_packed(S, plan, stage)) PM_LAUNCH((k_answer_p5k<2, kAnsPNT>));
+      else PM_LAUNCH((k_answer_p5<2, kAnsPNT>));
+      break;
+    case FORM_ANSWER_P:
+      if (step_answer_packed(S, plan, stage)) PM_LAUNCH((k_answer_pk<2, kAnsPNT>));
+      else PM_LAUNCH((k_answer_p<2, kAnsPNT>));
+      break;
     case FORM_ANSWER_S:
       if (L.block == 128) PM_LAUNCH_W(k_answer_s, 128);
       else if (L.block == 512) PM_LAUNCH_W(k_answer_s, 512);
