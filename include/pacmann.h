@@ -599,6 +599,31 @@ int pm_robust_prune_wide(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t
                          uint64_t nids, uint32_t m, float alpha, int presorted, uint32_t* out, uint32_t* out_len,
                          uint32_t* err);
 
+/* ---- 128 prefilter keys per query row ----------------- */
+/* pm_knn_wide, pm_build_graph_wide and pm_knn_stages_wide with 128 instead of
+ * 64 prefilter keys per query row, for every k and m: k in [1, 128] ("k must be
+ * in [1, 128]") and, in the build, m in [1, 64] ("m must be in [1, 64]": int(1.5
+ * m) + self = 97 keys); dim in [1, 1024] and every other rule as the _wide
+ * calls', all checked before any HIP call.  The prefilter distances are the
+ * 64-key kernels' bit for bit and eps is unchanged; tau is the 128th prefilter
+ * distance instead of the 64th, so for k <= 64 the uncertified rows are a subset
+ * of pm_knn_wide's: a caller who wants fewer brute-force rows gets them by
+ * name.  Rows with n <= 128 are never judged.  Timing names: "knn_prefilter_k128"
+ * (dp 128 / 192), "knn_prefilter_k128_w" (dp 256 .. 1,024, K chunks of 32),
+ * "knn_rerank", "knn_brute".  The result is the brute-force (L2Dist in
+ * l2_distance_amd64.s order, id) ranking, -1 / +inf padded, for every finite
+ * float input. */
+int pm_knn_k128(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                uint32_t k, int64_t* ids, float* dists, uint64_t* fallback_rows);
+/* pm_build_graph_wide for m in [1, 64]: equals the oracle's graph. */
+int pm_build_graph_k128(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
+                        uint64_t seed, uint32_t* graph, double* times, uint64_t* fallback_rows);
+/* Test probe: pm_knn_stages_wide with out->cand and out->pref [nq][128]; eps
+ * holds NaN bits where no row was judged (n <= 128). */
+int pm_knn_stages_k128(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                       uint32_t k, pm_knn_stages_out* out);
+uint32_t pm_knn_k128_top(void);   /* 128 */
+
 #ifdef __cplusplus
 }
 #endif

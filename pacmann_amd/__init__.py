@@ -148,6 +148,10 @@ SIGNATURES = {
     "pm_knn_stages_wide": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, C.POINTER(KnnStagesOut)]),
     "pm_robust_prune_wide": (C.c_int, [vp, f32p, u64, u64, u32p, u64, u64p, u32p, u32p, u64, C.c_uint32, C.c_float,
                                        C.c_int, u32p, u32p, u32p]),
+    "pm_knn_k128": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, i64p, f32p, u64p]),
+    "pm_build_graph_k128": (C.c_int, [vp, f32p, u64, u64, u64, C.c_float, u64, u32p, C.POINTER(dbl), u64p]),
+    "pm_knn_stages_k128": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, C.POINTER(KnnStagesOut)]),
+    "pm_knn_k128_top": (C.c_uint32, []),
     "pm_search_loop_sessions": (C.c_int, [C.POINTER(vp), C.c_uint32, f32p, u64, C.c_int, C.c_int, C.c_int,
                                           i64p, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "pm_batchpir_group_create": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
@@ -926,6 +930,12 @@ def knn_wide(base, queries, k: int, ctx: Context | None = None, with_dist: bool 
     return _knn_exact(lib().pm_knn_wide, base, queries, k, ctx, with_dist)
 
 
+def knn_k128(base, queries, k: int, ctx: Context | None = None, with_dist: bool = False):
+    """pm.knn_wide with 128 prefilter keys per query row: k up to 128, and fewer
+    brute-force rows at every k (pm_knn_k128)."""
+    return _knn_exact(lib().pm_knn_k128, base, queries, k, ctx, with_dist)
+
+
 def _knn_exact(fn, base, queries, k, ctx, with_dist):
     ctx = ctx or default_context()
     b = np.ascontiguousarray(base, dtype=np.float32)
@@ -944,7 +954,14 @@ def knn_stages_wide(base, queries, k: int, ctx: Context | None = None) -> dict:
     return knn_stages(base, queries, k, ctx, exact=True, wide=True)
 
 
-def knn_stages(base, queries, k: int, ctx: Context | None = None, exact: bool = True, wide: bool = False) -> dict:
+def knn_stages_k128(base, queries, k: int, ctx: Context | None = None) -> dict:
+    """pm_knn_stages_k128: pm.knn_stages_wide for pm.knn_k128; "cand" and "pref"
+    are [nq, 128]."""
+    return knn_stages(base, queries, k, ctx, exact=True, wide=True, top=128)
+
+
+def knn_stages(base, queries, k: int, ctx: Context | None = None, exact: bool = True, wide: bool = False,
+               top: int = 64) -> dict:
     """pm_knn_stages: what pm.knn (exact=False) or pm.knn_exact keeps inside for
     these rows.  "cand" [nq, 64] uint32 (0xffffffff: empty slot) and "pref"
     [nq, 64] float32, the prefilter's keys in order, and "dp"; exact adds "tau",
@@ -956,7 +973,7 @@ def knn_stages(base, queries, k: int, ctx: Context | None = None, exact: bool = 
     n, nq, dp = b.shape[0], q.shape[0], 192 if b.shape[1] > 128 else 128
     if wide and b.shape[1] > 192:
         dp = -(-b.shape[1] // 64) * 64
-    r = {"cand": np.zeros((nq, 64), np.uint32), "pref": np.zeros((nq, 64), np.float32)}
+    r = {"cand": np.zeros((nq, top), np.uint32), "pref": np.zeros((nq, top), np.float32)}
     if exact:
         r.update(tau=np.zeros(nq, np.float32), eps=np.zeros(nq, np.float32), qnorm=np.zeros(nq, np.float32),
                  bnorm=np.zeros(n, np.float32), maxnorm=np.zeros(1, np.uint32), bhi=np.zeros((n, dp), np.uint16),
@@ -965,7 +982,9 @@ def knn_stages(base, queries, k: int, ctx: Context | None = None, exact: bool = 
     for name, ctype in KnnStagesOut._fields_:
         if name in r:
             setattr(o, name, _p(r[name], ctype))
-    if wide:
+    if top == 128:
+        _check(lib().pm_knn_stages_k128(ctx.h, _p(b, f32p), n, b.shape[1], _p(q, f32p), nq, k, C.byref(o)))
+    elif wide:
         _check(lib().pm_knn_stages_wide(ctx.h, _p(b, f32p), n, b.shape[1], _p(q, f32p), nq, k, C.byref(o)))
     else:
         _check(lib().pm_knn_stages(ctx.h, _p(b, f32p), n, b.shape[1], _p(q, f32p), nq, k, int(exact), C.byref(o)))
@@ -1010,8 +1029,14 @@ def build_graph_wide(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Co
     return build_graph(vectors, m, alpha, seed, ctx, exact=True, wide=True)
 
 
+def build_graph_k128(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context | None = None):
+    """pm.build_graph_wide with 128 prefilter keys per row: m up to 64
+    (pm_build_graph_k128)."""
+    return build_graph(vectors, m, alpha, seed, ctx, exact=True, wide=True, k128=True)
+
+
 def build_graph(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context | None = None,
-                exact: bool = False, wide: bool = False):
+                exact: bool = False, wide: bool = False, k128: bool = False):
     """graphann.BuildGraph (build_graph.go:97-105,314-523) on the GPU with exact
     kNN candidates (pm_build_graph).  Returns (graph [n, m] uint32, times dict).
     exact=True: pm_build_graph_exact, whose candidates are exact for general
@@ -1022,7 +1047,7 @@ def build_graph(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context
     t = (dbl * 4)()
     fb = u64(0)
     if exact:
-        fn = lib().pm_build_graph_wide if wide else lib().pm_build_graph_exact
+        fn = lib().pm_build_graph_k128 if k128 else lib().pm_build_graph_wide if wide else lib().pm_build_graph_exact
         _check(fn(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], m, alpha, seed, _p(g, u32p), t, C.byref(fb)))
     else:
         _check(lib().pm_build_graph(ctx.h, _p(v, f32p), v.shape[0], v.shape[1], m, alpha, seed, _p(g, u32p), t))

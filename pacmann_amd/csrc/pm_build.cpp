@@ -33,6 +33,8 @@ struct KnnDev {   // device copies for the prefilter + re-rank
 // The "_wide" entry points: rows up to 1,024 wide.  Up to kWideFrom they take the
 // narrow path unchanged; above it the kernels of pm_graph_wide.hip.
 static const char* const kWideDimText = "dim must be in [1, 1024]";
+// The "_k128" entry points: the wide ones with 128 prefilter keys per query row.
+static const char* const kK128KText = "k must be in [1, 128]";
 constexpr uint32_t kWideFrom = 192;
 static bool wide_dim_ok(uint64_t dim) { return pmk::knn_pad_dim_wide((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)) != 0; }
 // exact: the split rows of pm_knn_exact (hi + lo, norms of the f32 values);
@@ -66,21 +68,26 @@ static int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDe
 // candidates' prefilter distances (pref [nq][64]) and, exact, each row's eps
 // (NaN bits where no row was judged: n <= 64); tau and the uncertified list
 // (nl rows, unordered) stay in the struct either way.
+// top: the keys kept per query row, knn_top() or, for the _k128 entry points
+// (exact only), knn_top_k128(): the kernels of pm_graph_k128.hip, cand and pref
+// [nq][128], no row judged for n <= 128.
 struct KnnOut {
   DevBuf cand, out, dist, len, tau, list, nlist, pref, eps;
   bool stages = false;
   uint64_t nl = 0;
 };
 static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, uint64_t nq, uint32_t dim, uint32_t K,
-                      bool self_base, bool want_dist, bool exact, KnnOut& o, uint64_t* fallback) {
+                      bool self_base, bool want_dist, bool exact, KnnOut& o, uint64_t* fallback,
+                      uint32_t top = pmk::knn_top()) {
   hipStream_t st = c->stream;
-  CHK(o.cand.reserve(std::max<uint64_t>(4, nq * pmk::knn_top() * 4)));
+  const bool k128 = top == pmk::knn_top_k128();
+  CHK(o.cand.reserve(std::max<uint64_t>(4, nq * top * 4)));
   CHK(o.out.reserve(std::max<uint64_t>(4, nq * K * 4)));
   if (want_dist) CHK(o.dist.reserve(std::max<uint64_t>(4, nq * K * 4)));
   CHK(o.len.reserve(std::max<uint64_t>(4, nq * 4)));
-  if (o.stages) CHK(o.pref.reserve(std::max<uint64_t>(4, nq * pmk::knn_top() * 4)));
+  if (o.stages) CHK(o.pref.reserve(std::max<uint64_t>(4, nq * top * 4)));
   uint32_t* pref = o.stages ? o.pref.as<uint32_t>() : nullptr;
-  const double pre_bytes = (double)nq * n * B.dp * 2, rr_bytes = (double)nq * pmk::knn_top() * dim * 4;
+  const double pre_bytes = (double)nq * n * B.dp * 2, rr_bytes = (double)nq * top * dim * 4;
   if (!exact) {
     c->timed("knn_prefilter", pre_bytes, [&] {
       pmk::knn_prefilter(st, B.xb.p, B.xn.as<float>(), n, Q.xb.p, Q.xn.as<float>(), nq, B.dp, o.cand.as<uint32_t>(),
@@ -99,7 +106,11 @@ static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, u
     HIPCHK(hipMemsetAsync(o.eps.p, 0xff, std::max<uint64_t>(4, nq * 4), st));
   }
   const bool wide = B.dp > kWideFrom;   // rows padded by knn_pad_dim_wide: the kernels of pm_graph_wide.hip
-  if (wide)
+  if (k128)
+    c->timed(wide ? "knn_prefilter_k128_w" : "knn_prefilter_k128", 2 * pre_bytes, [&] {
+      pmk::knn_prefilter_k128(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
+                              o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
+  else if (wide)
     c->timed("knn_prefilter_w", 2 * pre_bytes, [&] {
       pmk::knn_prefilter_x3_w(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
                               o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
@@ -108,7 +119,7 @@ static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, u
       pmk::knn_prefilter_x3(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
                             o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
   c->timed("knn_rerank", rr_bytes, [&] {
-    pmk::knn_rerank_cert(st, B.x.as<float>(), n, dim, Q.x.as<float>(), nq, o.cand.as<uint32_t>(), K, self_base,
+    (k128 ? pmk::knn_rerank_cert_k128 : pmk::knn_rerank_cert)(st, B.x.as<float>(), n, dim, Q.x.as<float>(), nq, o.cand.as<uint32_t>(), K, self_base,
                          o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>(), Q.xn.as<float>(),
                          o.tau.as<float>(), B.mx.as<uint32_t>(), B.dp, o.list.as<uint64_t>(), o.nlist.as<uint64_t>(),
                          o.stages ? o.eps.as<float>() : nullptr); });
@@ -116,7 +127,7 @@ static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, u
   HIPCHK(hipMemcpyAsync(&nl, o.nlist.p, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   c->timed("knn_brute", (double)nl * n * dim * 4, [&] {
-    (wide ? pmk::knn_brute_w : pmk::knn_brute)(st, B.x.as<float>(), n, dim, Q.x.as<float>(), o.list.as<uint64_t>(), nl,
+    (k128 ? pmk::knn_brute_k128 : wide ? pmk::knn_brute_w : pmk::knn_brute)(st, B.x.as<float>(), n, dim, Q.x.as<float>(), o.list.as<uint64_t>(), nl,
                                                K, self_base, o.out.as<uint32_t>(), o.dist.as<float>(),
                                                o.len.as<uint32_t>()); });
   HIPCHK(hipStreamSynchronize(st));
@@ -129,10 +140,11 @@ static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, u
 // id), k <= 64 (the ground truth of ComputeRecall, build_graph.go:821-863);
 // ids -1 padded.
 static int knn_impl(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
-                    uint32_t k, int64_t* ids, float* dists, bool exact, uint64_t* fallback, bool wide = false) {
+                    uint32_t k, int64_t* ids, float* dists, bool exact, uint64_t* fallback, bool wide = false,
+                    uint32_t top = pmk::knn_top()) {
   if (!c || !base || (!queries && nq) || (!ids && nq)) return fail(PM_EINVAL, "NULL argument");
   if (wide && !wide_dim_ok(dim)) return fail(PM_EINVAL, kWideDimText);
-  if (k == 0 || k > pmk::knn_top()) return fail(PM_EINVAL, "k must be in [1, 64]");
+  if (k == 0 || k > top) return fail(PM_EINVAL, top == pmk::knn_top() ? "k must be in [1, 64]" : kK128KText);
   if (n == 0 || dim == 0 || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be in [1, 2^32-1)");
   if (exact && !wide && !pmk::knn_pad_dim((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)))
     return fail(PM_EINVAL, "kNN supports dim <= 192");
@@ -141,7 +153,7 @@ static int knn_impl(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, cons
   CHK(knn_upload(c, base, n, (uint32_t)dim, B, exact, wide));
   CHK(knn_upload(c, queries, nq, (uint32_t)dim, Q, exact, wide));
   KnnOut o;
-  CHK(knn_device(c, B, n, Q, nq, (uint32_t)dim, k, false, true, exact, o, fallback));
+  CHK(knn_device(c, B, n, Q, nq, (uint32_t)dim, k, false, true, exact, o, fallback, top));
   std::vector<uint32_t> out(nq * k), l(nq);
   std::vector<float> dd(nq * k);
   HIPCHK(hipMemcpyAsync(out.data(), o.out.p, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
@@ -169,15 +181,22 @@ extern "C" int pm_knn_wide(pm_ctx* c, const float* base, uint64_t n, uint64_t di
   if (fallback_rows) *fallback_rows = 0;
   return knn_impl(c, base, n, dim, queries, nq, k, ids, dists, true, fallback_rows, true);
 }
+extern "C" int pm_knn_k128(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
+                           uint32_t k, int64_t* ids, float* dists, uint64_t* fallback_rows) {
+  if (fallback_rows) *fallback_rows = 0;
+  return knn_impl(c, base, n, dim, queries, nq, k, ids, dists, true, fallback_rows, true, pmk::knn_top_k128());
+}
+extern "C" uint32_t pm_knn_k128_top(void) { return pmk::knn_top_k128(); }
 
 // pm_knn_stages and pm_knn_stages_wide: pm_knn's (exact: pm_knn_exact's, wide:
 // pm_knn_wide's) own upload and launches (knn_upload, knn_device), with the
 // intermediate values copied out.
 static int knn_stages_impl(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries, uint64_t nq,
-                           uint32_t k, int exact, pm_knn_stages_out* out, bool wide) {
+                           uint32_t k, int exact, pm_knn_stages_out* out, bool wide,
+                           uint32_t top = pmk::knn_top()) {
   if (!c || !base || !queries || !out || !out->cand || !out->pref) return fail(PM_EINVAL, "NULL argument");
   if (wide && !wide_dim_ok(dim)) return fail(PM_EINVAL, kWideDimText);
-  if (k == 0 || k > pmk::knn_top()) return fail(PM_EINVAL, "k must be in [1, 64]");
+  if (k == 0 || k > top) return fail(PM_EINVAL, top == pmk::knn_top() ? "k must be in [1, 64]" : kK128KText);
   if (n == 0 || dim == 0 || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be in [1, 2^32-1)");
   if (nq == 0) return fail(PM_EINVAL, "nq must be > 0");
   if (!wide && !pmk::knn_pad_dim((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)))
@@ -189,11 +208,10 @@ static int knn_stages_impl(pm_ctx* c, const float* base, uint64_t n, uint64_t di
   CHK(knn_upload(c, queries, nq, (uint32_t)dim, Q, exact != 0, wide));
   KnnOut o;
   o.stages = true;
-  CHK(knn_device(c, B, n, Q, nq, (uint32_t)dim, k, false, true, exact != 0, o, nullptr));
+  CHK(knn_device(c, B, n, Q, nq, (uint32_t)dim, k, false, true, exact != 0, o, nullptr, top));
   auto get = [&](void* dst, const DevBuf& src, uint64_t bytes) {
     return dst ? hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
   };
-  const uint64_t top = pmk::knn_top();
   out->dp = B.dp;
   out->n_uncertified = 0;
   HIPCHK(get(out->cand, o.cand, nq * top * 4));
@@ -225,6 +243,10 @@ extern "C" int pm_knn_stages(pm_ctx* c, const float* base, uint64_t n, uint64_t 
 extern "C" int pm_knn_stages_wide(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries,
                                   uint64_t nq, uint32_t k, pm_knn_stages_out* out) {
   return knn_stages_impl(c, base, n, dim, queries, nq, k, 1, out, true);
+}
+extern "C" int pm_knn_stages_k128(pm_ctx* c, const float* base, uint64_t n, uint64_t dim, const float* queries,
+                                  uint64_t nq, uint32_t k, pm_knn_stages_out* out) {
+  return knn_stages_impl(c, base, n, dim, queries, nq, k, 1, out, true, pmk::knn_top_k128());
 }
 
 // robustPrune on the GPU of the listed vertices' lists (the second pass of the
@@ -306,12 +328,14 @@ static int prune_lists(pm_ctx* c, const float* X, uint64_t n, uint32_t dim, cons
 // pm_build_graph and pm_build_graph_exact
 static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
                             uint64_t seed, uint32_t* graph, double* times, bool exact, uint64_t* fallback,
-                            bool wide = false) {
+                            bool wide = false, uint32_t top = pmk::knn_top()) {
   if (!c || !vectors || !graph) return fail(PM_EINVAL, "NULL argument");
   if (wide && !wide_dim_ok(dim)) return fail(PM_EINVAL, kWideDimText);
   const uint32_t K = (uint32_t)((float)m * 1.5f);   // int(float32(m)*1.5) NGT results (build_graph.go:398)
-  if (m == 0 || m > pmk::prune_max_m() || K + 1 > pmk::knn_top())
-    return fail(PM_EINVAL, "m must be in [1, 42] (1.5 m candidates + self within the 64-key prefilter)");
+  if (m == 0 || m > pmk::prune_max_m() || K + 1 > top)
+    return fail(PM_EINVAL, top == pmk::knn_top()
+                               ? "m must be in [1, 42] (1.5 m candidates + self within the 64-key prefilter)"
+                               : "m must be in [1, 64] (1.5 m candidates + self within the 128-key prefilter)");
   if (!wide && (dim == 0 || dim > pmk::prune_max_dim() || !pmk::knn_pad_dim((uint32_t)dim)))
     return fail(PM_EINVAL, "dim must be in [1, 192]");
   if (n <= m || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be > m (the random fill needs m other vertices)");
@@ -327,7 +351,7 @@ static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_
   CHK(err.reserve(4));
   HIPCHK(hipMemsetAsync(err.p, 0, 4, st));
   // candidates: NGT.Search(u, 1.5m) with u removed (:398-410), exact here
-  CHK(knn_device(c, X, n, X, n, (uint32_t)dim, K, true, false, exact, kn, fallback));
+  CHK(knn_device(c, X, n, X, n, (uint32_t)dim, K, true, false, exact, kn, fallback, top));
   HIPCHK(hipStreamSynchronize(st));
   auto t1 = Clock::now();
   // first pass: robustPrune(vectors, u, candidates, m, alpha) (:413-414)
@@ -444,6 +468,12 @@ extern "C" int pm_build_graph_wide(pm_ctx* c, const float* vectors, uint64_t n, 
                                    uint64_t seed, uint32_t* graph, double* times, uint64_t* fallback_rows) {
   if (fallback_rows) *fallback_rows = 0;
   return build_graph_impl(c, vectors, n, dim, m, alpha, seed, graph, times, true, fallback_rows, true);
+}
+extern "C" int pm_build_graph_k128(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
+                                   uint64_t seed, uint32_t* graph, double* times, uint64_t* fallback_rows) {
+  if (fallback_rows) *fallback_rows = 0;
+  return build_graph_impl(c, vectors, n, dim, m, alpha, seed, graph, times, true, fallback_rows, true,
+                          pmk::knn_top_k128());
 }
 
 // pm_robust_prune and pm_robust_prune_wide: k_prune (wide, rows above kWideFrom:

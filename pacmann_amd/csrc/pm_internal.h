@@ -567,4 +567,18 @@ void prune_w(hipStream_t st, const float* X, uint32_t dim, const uint32_t* verts
              const uint64_t* offs, uint64_t stride, const uint32_t* lens, const uint32_t* ids, uint32_t m,
              float alpha, uint32_t* out, uint32_t* out_len, uint32_t* err, const uint32_t* sorted_pos = nullptr,
              const float* dist_g = nullptr);
+// 128 prefilter keys per query row (pm_graph_k128.hip; pm_knn_k128, pm_build_graph_k128): out and
+// out_hi are [M][128], tau the 128th prefilter distance, K up to 128.  knn_prefilter_k128 takes
+// every padded width (128, 192, or a multiple of 64 up to 1,024), knn_brute_k128 every dim up to
+// 1,024.  Arguments as knn_prefilter_x3_w, knn_rerank_cert and knn_brute.
+uint32_t knn_top_k128();
+void knn_prefilter_k128(hipStream_t st, const void* Xh, const void* Xl, const float* xn, uint64_t N, const void* Qh,
+                        const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau,
+                        uint32_t* out_hi = nullptr);
+void knn_rerank_cert_k128(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
+                          const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len,
+                          const float* qn, const float* tau, const uint32_t* maxnorm, uint32_t dp, uint64_t* list,
+                          uint64_t* nlist, float* eps_out = nullptr);
+void knn_brute_k128(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, const uint64_t* list,
+                    uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
 }  // namespace pmk
