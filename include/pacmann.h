@@ -91,7 +91,12 @@ int pm_timing_enable(pm_ctx* ctx, int level);
  * automatic / 0 / 1; "match_part8": its one-wave-per-block form where PH % 8 ==
  * 0, 0 / 1; "match_resolve": k_match_resolve* for search-sized steps, 0 / 1 /
  * 2 (the general form).  -2 restores the environment's choice (PM_MATCH_PART,
- * PM_MATCH_PART8, PM_MATCH_RESOLVE).  "aes_bs": the preprocessing's PRF tables
+ * PM_MATCH_PART8, PM_MATCH_RESOLVE).  "step_help": k_step's gather helpers per
+ * sub-query, 0..3 (-2: PM_STEP_HELP, default 3), still capped by the launch's
+ * workgroup budget (pm_step_plan's nhelp).  "step_help_spoil" (tests): a mask of
+ * helpers 1..3 (bits 0..2) that hand over their partial with a guess no answer
+ * accepts, so the answers refuse the helpers and gather again; no form, grid or
+ * result changes (-2 / 0: off); other values of either are PM_EINVAL.  "aes_bs": the preprocessing's PRF tables
  * by the bitsliced VALU AES (1) or the T-table AES (0, default; -1: PM_AES_BS).
  * "fold_rot": the hint fold of ChunkSize 512 / 1,024 partitions by the
  * bank-rotated kernel over a fold image of the DB (1) or by the pipelined fold
@@ -301,6 +306,23 @@ int  pm_batchpir_group_query(pm_batchpir_group* g, const uint64_t* ids, uint64_t
 int  pm_batchpir_group_preprocessing(pm_batchpir_group* g);
 void pm_batchpir_group_destroy(pm_batchpir_group* g);
 int  pm_batchpir_subconfig(pm_batchpir* h, uint64_t partition, pm_pir_config* cfg);
+/* The speculation record of this handle's last step (test hook), where the
+ * fused step kernel (k_step, "host_path_step") ran it on a context created with
+ * PM_STEP_SPEC=1: *nsub words in sub-query order (partition-major, qn slots per
+ * partition) into out[0 .. cap).  k_step's answers start on a guess of their
+ * resolution; each word says what became of one:
+ *   bits 0-2  the guessed answer mode: 1 final, 4 dummy, 7 no guess
+ *   bit  3    helped: the guessed set was gathered with the gather helpers
+ *   bit  4    help_ok: every helper's guess was the answer's (1 where not helped)
+ *   bit  5    kept: the resolution equals the guess in every field the answer reads
+ *   bit  6    redo: the set was gathered again for the resolution (!kept || !help_ok)
+ *   bits 8-10 the resolution's answer mode: 0 zero (failed / skipped), 1 final,
+ *             2 chained (its hint was refreshed earlier in the step), 3 cached, 4 dummy
+ *   bit  31   written by the kernel (always 1)
+ * out NULL with cap 0: *nsub alone.  PM_EINVAL for a NULL argument otherwise, a
+ * context without the record, a last step that did not run k_step (or none
+ * yet), or cap < *nsub (*nsub is set). */
+int  pm_batchpir_step_spec(pm_batchpir* h, uint32_t* out, uint64_t cap, uint64_t* nsub);
 
 /* State export of one partition's client (test hook; sizes from the config):
  * round_keys[44], primary_tag[PH], primary_parity[PH*E], primary_pp[PH],

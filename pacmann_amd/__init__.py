@@ -123,6 +123,7 @@ SIGNATURES = {
     "pm_batchpir_create_synth": (C.c_int, [vp, u64, u64, u64, u64, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
     "pm_batchpir_stats_get": (C.c_int, [vp, C.POINTER(BatchStats)]),
     "pm_batchpir_subconfig": (C.c_int, [vp, u64, C.POINTER(PirConfig)]),
+    "pm_batchpir_step_spec": (C.c_int, [vp, C.POINTER(C.c_uint32), u64, C.POINTER(u64)]),
     "pm_pir_export": (C.c_int, [vp, u32p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "pm_batchpir_export": (C.c_int, [vp, u64, u32p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "pm_graph_create": (C.c_int, [vp, u64, u64, u64, f32p, u32p, C.c_int, C.c_int, u64, u64, C.POINTER(vp)]),
@@ -334,6 +335,14 @@ def fold_image_map(cs: int, ss: int, E: int, dim: int = 0, packed: bool = False,
     _check(lib().pm_fold_image_map(cs, ss, E, dim, int(packed), x0, n, _p(row, u64p), _p(word, u32p), _p(pk, u8p),
                                    C.byref(nitems), C.byref(npk)))
     return row, word, pk.astype(bool), nitems.value, npk.value
+
+
+def step_spec_fields(word: int) -> dict:
+    """One word of SimpleBatchPianoPIR.step_spec (include/pacmann.h): gmode / mode are answer modes (0 zero,
+    1 final, 2 chained, 3 cached, 4 dummy; gmode 7: no guess)."""
+    w = int(word)
+    return dict(gmode=w & 7, helped=bool(w & 8), help_ok=bool(w & 16), kept=bool(w & 32), redo=bool(w & 64),
+                mode=(w >> 8) & 7, written=bool(w >> 31))
 
 
 def step_plan(kind: int, np_: int, nsub: int, max_per_part: int, maxPH: int, maxSS: int, E: int, *,
@@ -577,6 +586,15 @@ class SimpleBatchPianoPIR:
         s = BatchStats()
         _check(lib().pm_batchpir_stats_get(self.h, C.byref(s)))
         return s.asdict()
+
+    def step_spec(self) -> np.ndarray:
+        """pm_batchpir_step_spec: the speculation record of the last step (k_step on a context created with
+        PM_STEP_SPEC=1), one uint32 per sub-query in sub-query order; see step_spec_fields."""
+        n = u64(0)
+        _check(lib().pm_batchpir_step_spec(self.h, None, 0, C.byref(n)))   # the count first
+        out = np.zeros(n.value, dtype=np.uint32)
+        _check(lib().pm_batchpir_step_spec(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)), len(out), C.byref(n)))
+        return out[:n.value]
 
     def Config(self) -> dict:
         s = self.stats()

@@ -75,6 +75,8 @@ extern "C" int pm_ctx_create(int device, pm_ctx** out) {
   if (const char* rs = getenv("PM_REPL_SIDE")) c->repl_side = rs[0] != '0';
   const char* ng = getenv("PM_NO_GUESS");
   c->no_guess = ng && ng[0] == '1';
+  const char* sr = getenv("PM_STEP_SPEC");
+  c->step_spec = sr && sr[0] == '1';
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e != hipSuccess) { delete c; return fail(PM_EHIP, hipGetErrorString(e)); }
   *out = c;
@@ -161,6 +163,10 @@ extern "C" int pm_set_option(const char* name, int value) {
     pmk::set_answer_pack(value);
     return 0;
   }
+  if (!strcmp(name, "step_help") && value != -2 && (value < 0 || value > 3))
+    return fail(PM_EINVAL, "step_help takes 0..3 or -2");
+  if (!strcmp(name, "step_help_spoil") && value != -2 && (value < 0 || value > 7))
+    return fail(PM_EINVAL, "step_help_spoil takes a mask 0..7 or -2");
   if (pmk::set_option(name, value)) return fail(PM_EINVAL, std::string("unknown option ") + name);
   return 0;
 }

@@ -722,6 +722,7 @@ int step_chain(pm_ctx* c, StepBufs& B, PmStep& S, const pmk::StepShape& shape, u
   const pmk::StepPlan plan = pmk::step_plan(shape, pmk::step_opts());
   S.args_valid = shape.args_valid ? 1u : 0u;
   S.nsplit = plan.nsplit; S.qw = plan.qw; S.np_live = plan.np_live; S.cblk = plan.cblk; S.nhelp = plan.nhelp; S.no_guess = plan.no_guess;
+  S.help_spoil = plan.help_spoil;
   const uint32_t nsub = S.nsub;
   if (plan.qset) {
     CHK(B.qset.reserve((uint64_t)nsub * plan.qw * 2));
@@ -739,6 +740,13 @@ int step_chain(pm_ctx* c, StepBufs& B, PmStep& S, const pmk::StepShape& shape, u
       HIPCHK(hipMemsetAsync(B.helpg.p, 0, nh, st));
     }
     S.helpg = B.helpg.as<uint64_t>();
+  }
+  B.spec_nsub = 0;
+  if (fused && c->step_spec) {   // k_step's speculation record (pm_batchpir_step_spec), zeroed: 0 = never stored
+    CHK(B.specrec.reserve(kArgSubs * 4));
+    HIPCHK(hipMemsetAsync(B.specrec.p, 0, kArgSubs * 4, st));
+    S.specrec = B.specrec.as<uint32_t>();
+    B.spec_nsub = nsub;
   }
   // Timing level 2: the kernels carry their events in their own dispatch packets.
   auto run = [&](int stage, const char* name, double bytes) {
@@ -1342,6 +1350,20 @@ extern "C" int pm_batchpir_stats_get(pm_batchpir* h, pm_batchpir_stats* s) {
   s->FinishedBatchNum = g.FBN; s->QueriesMadeInPartition = g.QMIP; s->SupportBatchNum = g.Support;
   s->PrepCount = g.prepCount; s->LocalStorage = g.storage; s->PreprocessingTime = g.prepTime;
   s->CommOnline = g.commOn; s->CommOffline = g.commOff;
+  return 0;
+}
+extern "C" int pm_batchpir_step_spec(pm_batchpir* h, uint32_t* out, uint64_t cap, uint64_t* nsub) {
+  if (!h || !nsub || (!out && cap)) return fail(PM_EINVAL, "NULL argument");
+  Engine& g = h->e;
+  if (!g.ctx->step_spec) return fail(PM_EINVAL, "no speculation record: the context was created without PM_STEP_SPEC=1");
+  const uint32_t n = g.buf.spec_nsub;
+  if (!n) return fail(PM_EINVAL, "no speculation record: the last step did not run k_step");
+  *nsub = n;
+  if (!out) return 0;   // the count alone
+  if (cap < n) return fail(PM_EINVAL, "out holds fewer words than the step has sub-queries");
+  HIPCHK(hipSetDevice(g.ctx->device));
+  HIPCHK(hipStreamSynchronize(g.ctx->stream));
+  HIPCHK(hipMemcpy(out, g.buf.specrec.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return 0;
 }
 extern "C" int pm_batchpir_subconfig(pm_batchpir* h, uint64_t p, pm_pir_config* c) {

@@ -137,6 +137,8 @@ struct StepBufs {
   DevBuf subs_d, sb_d, bits, cand, meta, spec, res_d, ans, part_x, stamps;
   DevBuf qset;    // query sets expanded by k_match_resolve_s (PmStep::qset)
   DevBuf helpg;   // k_step's gather helpers' hand-off granules
+  DevBuf specrec;           // k_step's speculation record (PmStep::specrec; contexts of PM_STEP_SPEC=1)
+  uint32_t spec_nsub = 0;   // ... the sub-queries of the last step if k_step ran it with the record, else 0
   HostBuf desc_h, out_h;
   int reserve(uint32_t nsub, uint32_t np, uint32_t words, uint32_t cblk, uint64_t E) {
     CHK(subs_d.reserve(nsub * sizeof(PmSub)));

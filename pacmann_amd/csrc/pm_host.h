@@ -144,6 +144,7 @@ struct pm_ctx {
   bool no_fuse = false;      // PM_NO_FUSE=1: the three step kernels even when k_step fits
   bool no_split = false;     // PM_NO_SPLIT=1: k_answer gathers wide sets itself (no k_gather)
   bool no_guess = false;     // PM_NO_GUESS=1: k_step answers do not start before their resolution
+  bool step_spec = false;    // PM_STEP_SPEC=1: k_step keeps its speculation record (pm_batchpir_step_spec)
   bool verify_rows = false;  // PM_VERIFY_ROWS=1: re-read each step's results after the stream drains
   bool debug_cache = false;  // PM_DEBUG_CACHE=1: check cached answers against the slot's first answer
   bool log_steps = false;    // PM_LOG_STEPS=1: one stderr line per sub-query per step

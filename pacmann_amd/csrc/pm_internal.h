@@ -241,7 +241,14 @@ struct PmStep {
   // word of the partial, then the guess fields); 0 = none
   PM_G uint64_t* helpg;        // [kArgSubs][kStepHelpMax][kHelpGran]
   uint32_t nhelp;
-  PM_G uint32_t* err_h;        // pinned host: set when a hand-off spin timed out        // [np] k_step: token of the step whose results the resolver published
+  // "step_help_spoil" (tests): helper j (1..3) whose bit j - 1 is set gathers and hands over its partial as
+  // usual but publishes kNone as its guessed mode, so the answer refuses every helper's partial and redoes
+  uint32_t help_spoil;
+  // k_step's speculation record (contexts created with PM_STEP_SPEC=1; null: none): one word per
+  // sub-query, stored by its answer workgroup once it knows whether its speculative work stands
+  // (step_spec_word below), zeroed before the launch
+  PM_G uint32_t* specrec;      // [kArgSubs]
+  PM_G uint32_t* err_h;       // pinned host: set when a hand-off spin timed out        // [np] k_step: token of the step whose results the resolver published
   uint32_t words, E, dim, nsub, np, cblk;
   uint32_t np_live;            // partitions with at least one sub-query in this step
   uint32_t pf_w0, pf_w1;       // row words the host reads (PmOutHdr::csum covers them)
@@ -263,6 +270,20 @@ struct PmStep {
   uint32_t sb_a[kArgParts + 1];
   PmSub subs_a[kArgSubs];
 };
+
+// A word of k_step's speculation record (PmStep::specrec; pm_batchpir_step_spec returns them):
+//   bits 0-2  the guessed answer mode (step_guess): 1 A_FINAL, 4 A_DUMMY, 7 no guess
+//   bit  3    helped: the guess was gathered with the helpers (nhelp > 0 and a guess of A_FINAL / A_DUMMY)
+//   bit  4    help_ok: every helper's guess was the answer's (set where not helped)
+//   bit  5    kept: the resolution equals the guess in every field the answer reads
+//   bit  6    redo: the set was gathered again for the resolution (= !kept || !help_ok)
+//   bits 8-10 the resolution's answer mode (answer_mode): 0 A_ZERO, 1 A_FINAL, 2 A_CHAINED, 3 A_CACHED, 4 A_DUMMY
+//   bit  31   written (a word the step's kernel never stored reads 0)
+__host__ __device__ inline uint32_t step_spec_word(uint32_t gmode, bool helped, bool help_ok, bool kept, bool redo,
+                                                   uint32_t mode) {
+  return (gmode & 7u) | (helped ? 8u : 0u) | (help_ok ? 16u : 0u) | (kept ? 32u : 0u) | (redo ? 64u : 0u) |
+         ((mode & 7u) << 8) | 0x80000000u;
+}
 
 // ---- the device-resident team round (pm_drl.hip; pm_search_loop_batched's
 // device loop): a lock-step team's 20 rounds of SearchKNN +
@@ -409,9 +430,10 @@ struct PmEvents { hipEvent_t a = nullptr, b = nullptr; };
 int set_option(const char* name, int value);
 // The selectors' values for one step: pm_set_option's overrides over the environment's choices, each
 // read once per process (PM_MATCH_PART -1, PM_MATCH_PART8 1, PM_MATCH_RESOLVE 1, PM_ANSWER_WAVES 0,
-// PM_ANSWER_NT 128, PM_ANSWER_PAIR 1, PM_GATHER_SPLIT 0, PM_STEP_HELP 3).  One snapshot per step, so
-// a pm_set_option on another thread cannot split a step between two paths.
-struct StepOpts { int match_part, match_part8, match_resolve, answer_waves, answer_nt, answer_pair, gather_split, step_help; };
+// PM_ANSWER_NT 128, PM_ANSWER_PAIR 1, PM_GATHER_SPLIT 0, PM_STEP_HELP 3; "step_help" 0..3 overrides the
+// last, "step_help_spoil" has no variable and is 0 unless set).  One snapshot per step, so a
+// pm_set_option on another thread cannot split a step between two paths.
+struct StepOpts { int match_part, match_part8, match_resolve, answer_waves, answer_nt, answer_pair, gather_split, step_help, step_help_spoil; };
 StepOpts step_opts();
 uint32_t step_match_blocks(uint32_t maxPH);   // k_match workgroups per sub-query
 // Who builds the step: an engine's own step (engine_step: the device copies of
@@ -453,6 +475,7 @@ struct StepPlan {
   StepLaunch at[STAGE_COUNT];
   // the PmStep fields that must agree with the forms
   uint32_t nhelp, nsplit, qw, np_live, cblk, no_guess;
+  uint32_t help_spoil;   // PmStep::help_spoil ("step_help_spoil"; k_step only)
   bool qset;   // k_match_resolve_s expands the query sets (PmStep::qset, [nsub][qw]) and the answer reads them
 };
 // The one selection of a step's kernels, grids and fields: pure (no HIP call, environment or state).

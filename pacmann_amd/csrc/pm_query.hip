@@ -2105,6 +2105,9 @@ __device__ __forceinline__ void answer_role(const PmStep& S, uint32_t s, LDS& L)
                                            r.tag == g.tag && r.pp == g.pp));
     TS_SEEN(kept ? 1u : 0u);
     const bool redo = !kept || !help_ok;
+    // the speculation record (PmStep::specrec, contexts of PM_STEP_SPEC=1): which path this answer took
+    if (S.specrec && tid == 0)
+      S.specrec[s] = step_spec_word(gmode, helped, help_ok, kept, redo, mode);
     if (redo) {
       e_rv = e_bp = e_pp = 0;
       gather(r, mode, 0, P.SS);
@@ -2720,7 +2723,9 @@ __device__ __forceinline__ void helper_role(const PmStep& S, uint32_t s, uint32_
     }
   }
   if (tid < 6) {
-    const uint32_t f = tid == 0 ? gmode : tid == 1 ? g.hit : tid == 2 ? g.chunk : tid == 3 ? g.ing : tid == 4 ? g.tag : g.pp;
+    // a spoiled helper ("step_help_spoil" bit j - 1) hands over a guess that no answer's equals
+    const uint32_t g0 = (S.help_spoil >> (j - 1)) & 1u ? kNone : gmode;
+    const uint32_t f = tid == 0 ? g0 : tid == 1 ? g.hit : tid == 2 ? g.chunk : tid == 3 ? g.ing : tid == 4 ? g.tag : g.pp;
     put_g(out + 2 * kHelpWords + tid, f, S.token);
   }
 }
@@ -2781,7 +2786,7 @@ static const int env_match_part = env_int("PM_MATCH_PART", -1), env_match_part8 
                  env_answer_nt = env_int("PM_ANSWER_NT", 128), env_answer_pair = env_int("PM_ANSWER_PAIR", 1),
                  env_gather_split = env_int("PM_GATHER_SPLIT", 0), env_step_help = env_int("PM_STEP_HELP", 3);
 static std::atomic<int> ov_match_part{kOptUnset}, ov_match_part8{kOptUnset}, ov_match_resolve{kOptUnset},
-    ov_answer_waves{kOptUnset};
+    ov_answer_waves{kOptUnset}, ov_step_help{kOptUnset}, ov_step_help_spoil{kOptUnset};
 static int opt(const std::atomic<int>& ov, int env) {
   const int v = ov.load(std::memory_order_relaxed);
   return v != kOptUnset ? v : env;
@@ -2789,13 +2794,16 @@ static int opt(const std::atomic<int>& ov, int env) {
 StepOpts step_opts() {
   return StepOpts{opt(ov_match_part, env_match_part), opt(ov_match_part8, env_match_part8),
                   opt(ov_match_resolve, env_match_resolve), opt(ov_answer_waves, env_answer_waves),
-                  env_answer_nt, env_answer_pair, env_gather_split, env_step_help};
+                  env_answer_nt, env_answer_pair, env_gather_split, opt(ov_step_help, env_step_help),
+                  opt(ov_step_help_spoil, 0)};
 }
 int set_option(const char* name, int value) {
   std::atomic<int>* o = !strcmp(name, "match_part") ? &ov_match_part
                       : !strcmp(name, "match_part8") ? &ov_match_part8
                       : !strcmp(name, "match_resolve") ? &ov_match_resolve
-                      : !strcmp(name, "answer_waves") ? &ov_answer_waves : nullptr;
+                      : !strcmp(name, "answer_waves") ? &ov_answer_waves
+                      : !strcmp(name, "step_help") ? &ov_step_help
+                      : !strcmp(name, "step_help_spoil") ? &ov_step_help_spoil : nullptr;
   if (!o) return -1;
   o->store(value <= -2 ? kOptUnset : value, std::memory_order_relaxed);
   return 0;
@@ -2822,6 +2830,7 @@ StepPlan step_plan(const StepShape& s, const StepOpts& O) {
     // 32 sub-queries over 16 partitions take PM_STEP_HELP (default 3) each; 0 disables
     if (O.step_help > 0 && (s.E & ~3u) <= kHelpWords && 2 * s.nsub + s.np < kStepResidentWg)
       p.nhelp = std::min(std::min(kStepHelpMax, (uint32_t)O.step_help), (kStepResidentWg - 2 * s.nsub - s.np) / s.nsub);
+    p.help_spoil = (uint32_t)O.step_help_spoil & ((1u << kStepHelpMax) - 1);   // (tests) changes no form and no grid
     p.at[STAGE_FUSED] = {FORM_STEP, 2 * s.nsub + s.np + p.nhelp * s.nsub, 1, kStepBlock};
     return p;
   }

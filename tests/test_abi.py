@@ -15,7 +15,7 @@ def declared_symbols():
 
 def test_header_declares_api():
     syms = declared_symbols()
-    for s in ("pm_ctx_create", "pm_prf_batch", "pm_pir_server_answer", "pm_batchpir_query",
+    for s in ("pm_ctx_create", "pm_prf_batch", "pm_pir_server_answer", "pm_batchpir_query", "pm_batchpir_step_spec",
               "pm_search_knn", "pm_l2_batch", "pm_ip_bench"):
         assert s in syms
 
@@ -68,6 +68,25 @@ def test_last_error_crosses_files():
         assert L.pm_last_error() == b"ctx is NULL"
         assert call() == PM_EINVAL, layer
         assert L.pm_last_error() == want, layer
+
+
+def test_step_spec_argument_checks():
+    """pm_batchpir_step_spec checks its arguments before it touches the handle or the device; the texts of its
+    other refusals (a context without the record, a last step that was not k_step's) are pinned where a step can
+    run: tests/test_gpu_step_spec.py::test_step_spec_errors."""
+    import pacmann_amd as pm
+    L = pm.lib()
+    out, n = (C.c_uint32 * 4)(), C.c_uint64(0)
+    handle = C.c_void_p(1)   # never dereferenced: a NULL argument is refused first
+    for args in ((None, out, 4, C.byref(n)), (handle, None, 4, C.byref(n)), (handle, out, 4, None),
+                 (None, None, 0, C.byref(n)), (handle, None, 0, None)):
+        assert L.pm_ctx_mem_info(None, None, None) == -1 and L.pm_last_error() == b"ctx is NULL"
+        assert L.pm_batchpir_step_spec(*args) == -1
+        assert L.pm_last_error() == b"NULL argument"
+    assert pm.step_spec_fields(0x80000000 | 1 | 8 | 16 | 32 | (1 << 8)) == dict(
+        gmode=1, helped=True, help_ok=True, kept=True, redo=False, mode=1, written=True)
+    assert pm.step_spec_fields(0x80000000 | 7 | 64 | (3 << 8)) == dict(
+        gmode=7, helped=False, help_ok=False, kept=False, redo=True, mode=3, written=True)
 
 
 def test_build_lists_cover_csrc():

@@ -70,14 +70,17 @@ def assert_forms(ctxs, steps, forms, nhelp=0):
 
 
 class Case:
-    def __init__(self, name, forms, P, rows, E, F, qn, geom, S=1, fixture="ctx", batches=2, nhelp=0, opts=None, seed=0):
+    def __init__(self, name, forms, P, rows, E, F, qn, geom, S=1, fixture="ctx", batches=2, nhelp=0, opts=None, seed=0,
+                 ids=None):
         self.name, self.forms, self.P, self.rows, self.E, self.F, self.qn = name, forms, P, rows, E, F, qn
         self.geom, self.S, self.fixture, self.batches, self.nhelp = geom, S, fixture, batches, nhelp
         self.opts, self.seed = opts or {}, seed
+        self.ids = ids   # a function (case, db) -> ids [batches, S, n] instead of inputs()' seeded ones (cached per shape)
         self.N, self.n, self.np, self.nsub = P * rows, P * qn, S * P, S * P * qn
 
     def shape(self):   # what the inputs and the oracle's run depend on
-        return (self.P, self.rows, self.E, self.F, self.qn, self.S, self.batches, self.seed)
+        return (self.P, self.rows, self.E, self.F, self.qn, self.S, self.batches, self.seed,
+                self.ids.__name__ if self.ids else None)
 
 
     def plan(self):
@@ -149,10 +152,18 @@ BY_NAME = {c.name: c for c in CASES}
 PAIR = ("mr_s2-512", "mr_general-512")   # run together by test_match_resolve_general_equals_small
 
 
+_built_ids = {}
+
+
 def inputs(case):
     """The DB, the ids [batches, S, n] and the clients' seeds.  Planted: position 3 repeats position 1 inside
     every batch, and positions 0 and 2 of every later batch repeat the first batch's (the local cache)."""
     db = np.random.default_rng(1000 * case.rows + case.E).integers(0, 2**64, size=case.N * case.E, dtype=np.uint64)
+    if case.ids:
+        if case.shape() not in _built_ids:
+            _built_ids[case.shape()] = case.ids(case, db)
+            _built_ids[case.shape()].setflags(write=False)
+        return db, _built_ids[case.shape()], [SEED + 31 * i for i in range(case.S)]
     rng = np.random.default_rng([case.seed, case.rows, case.n, case.S])
     ids = rng.integers(0, case.N, size=(case.batches, case.S, case.n), dtype=np.uint64)
     ids[:, :, 3] = ids[:, :, 1]
@@ -189,6 +200,7 @@ def branch_counts(case, ids, want):
 
 
 _reference = {}
+_before = {}
 
 
 def oracle_run(oracle, case):
@@ -200,18 +212,33 @@ def oracle_run(oracle, case):
         ors = [oracle.SimpleBatchPianoPIR(case.N, case.E * 8, 2 * case.P, db, case.F, seed=sd) for sd in seeds]
         for o in ors:
             o.Preprocessing()
-        want = np.stack([np.stack([o.Query(ids[b, i])[0] for i, o in enumerate(ors)]) for b in range(case.batches)])
+        keep = case.S == 1 and case.forms == ("step",)   # k_step's cases: every partition's state before each batch too
+        before, want = [], []
+        for b in range(case.batches):
+            if keep:
+                before.append([ors[0].sub(p).export_state() for p in range(case.P)])
+            want.append(np.stack([o.Query(ids[b, i])[0] for i, o in enumerate(ors)]))
+        want = np.stack(want)
         state = [[o.sub(p).export_state() for p in range(case.P)] for o in ors]
         cfg = [ors[0].sub(p).Config() for p in range(case.P)]
         stats = [o.stats() for o in ors]
         for a in (want, *[x[k] for st in state for x in st for k in STATE_KEYS]):
             a.setflags(write=False)
         _reference[key] = (want, state, stats, cfg)
+        _before[key] = before
     return _reference[key]
 
 
-def run_case(case, request, oracle):
-    """Runs `case` on the product with every assertion of the module docstring; returns what it answered."""
+def oracle_before(oracle, case):
+    """Of a one-client k_step case: per batch, every partition's exported state before it (the same oracle run)."""
+    oracle_run(oracle, case)
+    assert case.S == 1 and case.forms == ("step",)
+    return _before[case.shape()]
+
+
+def run_case(case, request, oracle, step_hook=None):
+    """Runs `case` on the product with every assertion of the module docstring; returns what it answered.
+    step_hook(server), if given, is called after every batch (one step); its results are returned as well."""
     import pacmann_amd as pm
     ctx = request.getfixturevalue(case.fixture)
     db, ids, seeds = inputs(case)
@@ -239,10 +266,12 @@ def run_case(case, request, oracle):
             c.Preprocessing()
         grp = pm.BatchPIRGroup(clients) if case.S > 1 else None
         ctx.timing_reset()
-        answers = []
+        answers, hooked = [], []
         for b in range(case.batches):
             got, ok = grp.QueryWithMask(ids[b]) if grp else (x[None] for x in server.QueryWithMask(ids[b, 0]))
             answers.append((got, ok))
+            if step_hook:
+                hooked.append(step_hook(server))
             assert np.array_equal(got, want[b]), b
             for i in range(case.S):
                 r = rows[ids[b, i].astype(np.int64)]
@@ -263,7 +292,7 @@ def run_case(case, request, oracle):
                 for k in STATE_KEYS:
                     assert np.array_equal(a[k], state[i][p][k]), (i, p, k)
                 states.append(a)
-        return answers, states
+        return (answers, states, hooked) if step_hook else (answers, states)
     finally:
         for k in case.opts:
             pm.set_option(k, -2)

@@ -126,6 +126,12 @@ ROWS = [
     ("opt-match_resolve2", SHARED, 128, 4, {"opts": {"match_resolve": 2}}, ("mr_general", "answer_s"), {"np_live": 128}),
     ("opt-answer_waves5", SHARED, 128, 4, {"E": 100, "opts": {"answer_waves": 5}}, ("mr_s2", "answer_p5"), {}),
     ("opt-answer_waves6", SHARED, 128, 4, {"opts": {"answer_waves": 6}}, ("mr_s2", "answer_p"), {}),
+    # "step_help" over PM_STEP_HELP: fewer helpers than the budget's 3 (27 fit), never more than the budget's
+    ("opt-step_help0", ENGINE, 4, 2, {"opts": {"step_help": 0}}, ("step",), {"nhelp": 0}),
+    ("opt-step_help2", ENGINE, 4, 2, {"opts": {"step_help": 2}}, ("step",), {"nhelp": 2}),
+    ("opt-step_help3", ENGINE, 4, 2, {"opts": {"step_help": 3}}, ("step",), {"nhelp": 3}),
+    ("opt-step_help3-budget1", ENGINE, 32, 2, {"PH": 256, "SS": 8, "opts": {"step_help": 3}}, ("step",), {"nhelp": 1}),   # step-nhelp1
+    ("opt-step_help2-E260", ENGINE, 4, 2, {"E": 260, "opts": {"step_help": 2}}, ("step",), {"nhelp": 0}),
 ]
 
 
@@ -151,6 +157,30 @@ def test_grids():
     assert plan(SHARED, 129, 5, PH=7168, SS=68, E=4, opts={"answer_waves": 6})["launches"] == {
         "match_resolve": ("mr_s4", 129, 1, 256), "answer": ("answer_p", 323, 1, 128)}   # 645 sub-queries in pairs
     assert plan(SHARED, 128, 4, PH=16384)["launches"]["match_resolve"] == ("mr_general", 128, 1, 512)
+
+
+@pytest.mark.parametrize("shape", [(ENGINE, 4, 2, {}), (ENGINE, 32, 2, {"PH": 256, "SS": 8}), (ENGINE, 28, 4, {}),
+                                   (SHARED, 128, 4, {}), (ENGINE, 2, 65, {"PH": 1792})],
+                         ids=["nhelp3", "nhelp1", "nhelp0", "shared", "unfused"])
+def test_spoil_changes_no_plan(shape):
+    """ "step_help_spoil" (a helper's guess no answer accepts) changes no form, grid or field of any plan."""
+    kind, np_, qn, kw = shape
+    want = plan(kind, np_, qn, **kw)
+    for mask in (1, 2, 4, 7):
+        assert plan(kind, np_, qn, opts={"step_help_spoil": mask}, **kw) == want, mask
+        assert plan(kind, np_, qn, opts={"step_help_spoil": mask, "step_help": 2}, **kw) == \
+            plan(kind, np_, qn, opts={"step_help": 2}, **kw), mask
+    assert plan(kind, np_, qn, **kw) == want   # -2 restored both
+
+
+def test_step_help_option_values():
+    import pacmann_amd as pm
+    for name, bad, text in (("step_help", (-1, 4), "step_help takes 0..3 or -2"),
+                            ("step_help_spoil", (-1, 8), "step_help_spoil takes a mask 0..7 or -2")):
+        for v in bad:
+            with pytest.raises(RuntimeError, match=text):
+                pm.set_option(name, v)
+        pm.set_option(name, -2)
 
 
 def test_rejects():
