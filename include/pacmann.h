@@ -646,6 +646,32 @@ int pm_knn_stages_k128(pm_ctx* ctx, const float* base, uint64_t n, uint64_t dim,
                        uint32_t k, pm_knn_stages_out* out);
 uint32_t pm_knn_k128_top(void);   /* 128 */
 
+/* ---- uint8 rows on the int8 matrix cores -------------- */
+/* pm_knn and pm_build_graph for rows of bytes (SIFT / BIGANN .bvecs), which go
+ * to the device as bytes.  For values 0..255 and dim <= 256 every squared
+ * distance is an integer <= 256 * 255^2 < 2^24, so every term and partial sum of
+ * L2Dist is exact in f32 in any order: the integer distance converted to float
+ * is the reference's L2Dist bit for bit, and the (integer distance, id) ranking
+ * is the (L2Dist, id) ranking.  That is where the limit comes from: dim in
+ * [1, 256] ("dim must be in [1, 256]").  There is no re-rank, no certificate
+ * and no fallback, hence no fallback_rows.  k in [1, 128] ("k must be in [1,
+ * 128]"), n in [1, 2^32-1) ("n must be in [1, 2^32-1)"), ids -1 and dists +inf
+ * padded for k > n, dists may be NULL; all rules are checked before any HIP
+ * call.  Device memory of the kNN call: n dp + 4 n bytes for the base (dp: dim
+ * rounded up to a multiple of 64), the same for the queries, and a staging
+ * buffer of at most 32 MiB.  Timing names: "u8_bias", "knn_prefilter_u8". */
+int pm_knn_u8(pm_ctx* ctx, const uint8_t* base, uint64_t n, uint64_t dim, const uint8_t* queries, uint64_t nq,
+              uint32_t k, int64_t* ids, float* dists);
+/* pm_build_graph_k128 for byte rows, m in [1, 64] ("m must be in [1, 64] ..."),
+ * n > m: the candidates come from the integer kNN; the robustPrune stages, the
+ * host edge work and the fill are pm_build_graph's, over an f32 copy of the rows
+ * made on the device ("u8_to_f32"), so the build (not the kNN call) also holds
+ * n dim 4 bytes there.  times as pm_build_graph's four.  Equals the oracle's
+ * graph of the rows as floats. */
+int pm_build_graph_u8(pm_ctx* ctx, const uint8_t* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
+                      uint64_t seed, uint32_t* graph, double* times);
+uint32_t pm_knn_u8_max_dim(void);   /* 256 */
+
 #ifdef __cplusplus
 }
 #endif

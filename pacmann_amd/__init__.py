@@ -153,6 +153,9 @@ SIGNATURES = {
     "pm_build_graph_k128": (C.c_int, [vp, f32p, u64, u64, u64, C.c_float, u64, u32p, C.POINTER(dbl), u64p]),
     "pm_knn_stages_k128": (C.c_int, [vp, f32p, u64, u64, f32p, u64, C.c_uint32, C.POINTER(KnnStagesOut)]),
     "pm_knn_k128_top": (C.c_uint32, []),
+    "pm_knn_u8": (C.c_int, [vp, u8p, u64, u64, u8p, u64, C.c_uint32, i64p, f32p]),
+    "pm_build_graph_u8": (C.c_int, [vp, u8p, u64, u64, u64, C.c_float, u64, u32p, C.POINTER(dbl)]),
+    "pm_knn_u8_max_dim": (C.c_uint32, []),
     "pm_search_loop_sessions": (C.c_int, [C.POINTER(vp), C.c_uint32, f32p, u64, C.c_int, C.c_int, C.c_int,
                                           i64p, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "pm_batchpir_group_create": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
@@ -964,6 +967,46 @@ def _knn_exact(fn, base, queries, k, ctx, with_dist):
     _check(fn(ctx.h, _p(b, f32p), b.shape[0], b.shape[1], _p(q, f32p), q.shape[0], k, _p(ids, i64p), _p(d, f32p),
               C.byref(fb)))
     return (ids, d, int(fb.value)) if with_dist else (ids, int(fb.value))
+
+
+def _u8_rows(a, name: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype != np.uint8:   # no silent cast: float rows belong to the float entry points
+        raise TypeError(f"{name} must be uint8, got {a.dtype}")
+    return np.ascontiguousarray(a)
+
+
+def knn_u8_max_dim() -> int:
+    """The widest row of pm.knn_u8 / pm.build_graph_u8 (256: above it a squared
+    distance of bytes can pass 2^24 and stop being exact in float32)."""
+    return int(lib().pm_knn_u8_max_dim())
+
+
+def knn_u8(base, queries, k: int, ctx: Context | None = None, with_dist: bool = False):
+    """pm.knn for uint8 rows (pm_knn_u8): the rows go to the device as bytes and
+    the int8 matrix cores compute the integer distances, which are L2Dist bit for
+    bit for dim <= 256; k up to 128, no fallback.  TypeError unless both arrays
+    are uint8."""
+    b = _u8_rows(base, "base")
+    q = _u8_rows(queries, "queries").reshape(-1, b.shape[1])
+    ctx = ctx or default_context()
+    ids = np.zeros((q.shape[0], k), dtype=np.int64)
+    d = np.zeros((q.shape[0], k), dtype=np.float32)
+    _check(lib().pm_knn_u8(ctx.h, _p(b, u8p), b.shape[0], b.shape[1], _p(q, u8p), q.shape[0], k, _p(ids, i64p),
+                           _p(d, f32p)))
+    return (ids, d) if with_dist else ids
+
+
+def build_graph_u8(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context | None = None):
+    """pm.build_graph_k128 for uint8 rows (pm_build_graph_u8): m up to 64, dim up
+    to 256.  Returns (graph [n, m] uint32, times dict).  TypeError unless
+    vectors is uint8."""
+    v = _u8_rows(vectors, "vectors")
+    ctx = ctx or default_context()
+    g = np.zeros((v.shape[0], m), dtype=np.uint32)
+    t = (dbl * 4)()
+    _check(lib().pm_build_graph_u8(ctx.h, _p(v, u8p), v.shape[0], v.shape[1], m, alpha, seed, _p(g, u32p), t))
+    return g, {"knn_s": t[0], "prune1_s": t[1], "host_edges_s": t[2], "prune2_s": t[3]}
 
 
 def knn_stages_wide(base, queries, k: int, ctx: Context | None = None) -> dict:

@@ -17,7 +17,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libpacmann.so"
 SOURCES = [CSRC / "pm_kernels.hip", CSRC / "pm_query.hip", CSRC / "pm_graph.hip", CSRC / "pm_graph_wide.hip",
-           CSRC / "pm_graph_k128.hip",
+           CSRC / "pm_graph_k128.hip", CSRC / "pm_graph_u8.hip",
            CSRC / "pm_shard.hip",
            CSRC / "pm_drl.hip", CSRC / "pm_knnb.hip", CSRC / "pm_ctx.cpp", CSRC / "pm_engine.cpp",
            CSRC / "pm_search.cpp", CSRC / "pm_group.cpp", CSRC / "pm_devloop.cpp",

@@ -1,5 +1,6 @@
 // pm_build.cpp — graph construction and the exact kNN ground truth
-// (pm_knn, pm_build_graph).
+// (pm_knn, pm_build_graph), for float rows and for uint8 rows (pm_knn_u8,
+// pm_build_graph_u8).
 #include "pm_host.h"
 
 // ---------------------------------------------------------------------------
@@ -325,39 +326,40 @@ static int prune_lists(pm_ctx* c, const float* X, uint64_t n, uint32_t dim, cons
   return 0;
 }
 
-// pm_build_graph and pm_build_graph_exact
-static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
-                            uint64_t seed, uint32_t* graph, double* times, bool exact, uint64_t* fallback,
-                            bool wide = false, uint32_t top = pmk::knn_top()) {
-  if (!c || !vectors || !graph) return fail(PM_EINVAL, "NULL argument");
-  if (wide && !wide_dim_ok(dim)) return fail(PM_EINVAL, kWideDimText);
-  const uint32_t K = (uint32_t)((float)m * 1.5f);   // int(float32(m)*1.5) NGT results (build_graph.go:398)
-  if (m == 0 || m > pmk::prune_max_m() || K + 1 > top)
-    return fail(PM_EINVAL, top == pmk::knn_top()
-                               ? "m must be in [1, 42] (1.5 m candidates + self within the 64-key prefilter)"
-                               : "m must be in [1, 64] (1.5 m candidates + self within the 128-key prefilter)");
-  if (!wide && (dim == 0 || dim > pmk::prune_max_dim() || !pmk::knn_pad_dim((uint32_t)dim)))
-    return fail(PM_EINVAL, "dim must be in [1, 192]");
-  if (n <= m || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be > m (the random fill needs m other vertices)");
+// What the candidate stage hands to the rest of the build: the device f32 rows
+// and every vertex's candidates (out [n][K], len [n] valid each).
+struct BuildCand {
+  const float* x = nullptr;
+  const uint32_t* out = nullptr;
+  const uint32_t* len = nullptr;
+};
+
+// The build after its argument checks.  upload() puts the rows on the device,
+// candidates(bc) enqueues the exact kNN of every vertex (K results, self
+// dropped) and fills bc; everything else is the same for every entry point: the
+// first robustPrune, the host edge work, prune_lists and the fill, all over
+// bc.x.
+template <class Up, class Cand>
+static int build_graph_core(pm_ctx* c, uint64_t n, uint64_t dim, uint64_t m, float alpha, uint64_t seed,
+                            uint32_t* graph, double* times, bool wide, uint32_t K, Up&& upload, Cand&& candidates) {
   HIPCHK(hipSetDevice(c->device));
   hipStream_t st = c->stream;
   auto t0 = Clock::now();
-  KnnDev X;
-  CHK(knn_upload(c, vectors, n, (uint32_t)dim, X, exact, wide));
-  KnnOut kn;
+  CHK(upload());
   DevBuf g1, len1, err;
   CHK(g1.reserve(n * m * 4));
   CHK(len1.reserve(n * 4));
   CHK(err.reserve(4));
   HIPCHK(hipMemsetAsync(err.p, 0, 4, st));
   // candidates: NGT.Search(u, 1.5m) with u removed (:398-410), exact here
-  CHK(knn_device(c, X, n, X, n, (uint32_t)dim, K, true, false, exact, kn, fallback, top));
+  BuildCand bc;
+  CHK(candidates(bc));
   HIPCHK(hipStreamSynchronize(st));
   auto t1 = Clock::now();
   // first pass: robustPrune(vectors, u, candidates, m, alpha) (:413-414)
   c->timed("prune", 0.0, [&] {
     (wide && dim > kWideFrom ? pmk::prune_w : pmk::prune)(
-        st, X.x.as<float>(), (uint32_t)dim, nullptr, n, nullptr, K, kn.len.as<uint32_t>(), kn.out.as<uint32_t>(),
+        st, bc.x, (uint32_t)dim, nullptr, n, nullptr, K, bc.len, bc.out,
         (uint32_t)m, alpha, g1.as<uint32_t>(), len1.as<uint32_t>(), err.as<uint32_t>(), nullptr, nullptr); });
   std::vector<uint32_t> G(n * m), L1(n);
   uint32_t e = 0;
@@ -421,8 +423,7 @@ static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_
   auto t3 = Clock::now();
   if (!big.empty() || !huge.empty()) {
     std::vector<uint32_t> P, PL;
-    CHK(prune_lists(c, X.x.as<float>(), n, (uint32_t)dim, big, huge, coff, clen2, conn, (uint32_t)m, alpha, P, PL, &e,
-                    wide));
+    CHK(prune_lists(c, bc.x, n, (uint32_t)dim, big, huge, coff, clen2, conn, (uint32_t)m, alpha, P, PL, &e, wide));
     if (e) return fail(PM_EINVAL, "robustPrune: a connection list above the kernel's limit");
     for (const auto* lst : {&big, &huge})
       for (uint32_t u : *lst) {   // robustPrune of a list > m returns exactly m
@@ -454,6 +455,32 @@ static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_
   }
   return 0;
 }
+
+// pm_build_graph and pm_build_graph_exact
+static int build_graph_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
+                            uint64_t seed, uint32_t* graph, double* times, bool exact, uint64_t* fallback,
+                            bool wide = false, uint32_t top = pmk::knn_top()) {
+  if (!c || !vectors || !graph) return fail(PM_EINVAL, "NULL argument");
+  if (wide && !wide_dim_ok(dim)) return fail(PM_EINVAL, kWideDimText);
+  const uint32_t K = (uint32_t)((float)m * 1.5f);   // int(float32(m)*1.5) NGT results (build_graph.go:398)
+  if (m == 0 || m > pmk::prune_max_m() || K + 1 > top)
+    return fail(PM_EINVAL, top == pmk::knn_top()
+                               ? "m must be in [1, 42] (1.5 m candidates + self within the 64-key prefilter)"
+                               : "m must be in [1, 64] (1.5 m candidates + self within the 128-key prefilter)");
+  if (!wide && (dim == 0 || dim > pmk::prune_max_dim() || !pmk::knn_pad_dim((uint32_t)dim)))
+    return fail(PM_EINVAL, "dim must be in [1, 192]");
+  if (n <= m || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be > m (the random fill needs m other vertices)");
+  KnnDev X;
+  KnnOut kn;
+  return build_graph_core(
+      c, n, dim, m, alpha, seed, graph, times, wide, K,
+      [&] { return knn_upload(c, vectors, n, (uint32_t)dim, X, exact, wide); },
+      [&](BuildCand& bc) {
+        CHK(knn_device(c, X, n, X, n, (uint32_t)dim, K, true, false, exact, kn, fallback, top));
+        bc = {X.x.as<float>(), kn.out.as<uint32_t>(), kn.len.as<uint32_t>()};
+        return 0;
+      });
+}
 extern "C" int pm_build_graph(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
                               uint64_t seed, uint32_t* graph, double* times) {
   return build_graph_impl(c, vectors, n, dim, m, alpha, seed, graph, times, false, nullptr);
@@ -474,6 +501,106 @@ extern "C" int pm_build_graph_k128(pm_ctx* c, const float* vectors, uint64_t n, 
   if (fallback_rows) *fallback_rows = 0;
   return build_graph_impl(c, vectors, n, dim, m, alpha, seed, graph, times, true, fallback_rows, true,
                           pmk::knn_top_k128());
+}
+
+// ---------------------------------------------------------------------------
+// uint8 rows (pm_knn_u8, pm_build_graph_u8; pm_graph_u8.hip):
+// for values 0..255 and dim <= 256 the integer distance of the int8 matrix
+// cores is L2Dist bit for bit, so the candidate stage is two kernels (k_u8_bias,
+// k_knn_i8) with no re-rank, certificate or fallback.  The kNN call holds
+// n dp + 4 n bytes of the base on the device (dp: dim padded to 64) and a
+// staging buffer of at most kU8Stage bytes.  The build also holds the rows as
+// f32 (n dim 4 bytes, k_u8_to_f32): robustPrune reads f32 rows.
+// ---------------------------------------------------------------------------
+static const char* const kU8DimText = "dim must be in [1, 256]";
+constexpr uint64_t kU8Stage = 32ull << 20;   // bytes of raw rows on the device at a time
+struct KnnDevU8 {
+  DevBuf xb, xc, xf;   // biased padded rows, their constants, build: f32 rows
+  uint32_t dp = 0;
+};
+// The rows go up in pieces of at most kU8Stage bytes through one staging buffer
+// (the stream orders a piece's kernels before the next piece's copy).
+static int knn_upload_u8(pm_ctx* c, const uint8_t* v, uint64_t n, uint32_t dim, KnnDevU8& d, bool want_f32) {
+  hipStream_t st = c->stream;
+  d.dp = pmk::knn_u8_pad_dim(dim);
+  if (!d.dp) return fail(PM_EINVAL, kU8DimText);
+  CHK(d.xb.reserve(std::max<uint64_t>(4, n * d.dp)));
+  CHK(d.xc.reserve(std::max<uint64_t>(4, n * 4)));
+  if (want_f32) CHK(d.xf.reserve(std::max<uint64_t>(4, n * dim * 4)));
+  const uint64_t per = std::max<uint64_t>(1, kU8Stage / dim);
+  DevBuf stage;
+  CHK(stage.reserve(std::max<uint64_t>(4, std::min(n, per) * dim)));
+  for (uint64_t r0 = 0; r0 < n; r0 += per) {
+    const uint64_t rows = std::min(per, n - r0);
+    HIPCHK(hipMemcpyAsync(stage.p, v + r0 * dim, rows * dim, hipMemcpyHostToDevice, st));
+    c->timed("u8_bias", (double)rows * dim, [&] {
+      pmk::u8_bias(st, stage.as<uint8_t>(), rows, dim, d.dp, d.xb.as<uint8_t>() + r0 * d.dp, d.xc.as<int32_t>() + r0); });
+    if (want_f32)
+      c->timed("u8_to_f32", (double)rows * dim * 5, [&] {
+        pmk::u8_to_f32(st, stage.as<uint8_t>(), rows * dim, d.xf.as<float>() + r0 * dim); });
+  }
+  HIPCHK(hipStreamSynchronize(st));   // the staging buffer goes away here
+  return 0;
+}
+static void knn_i8_timed(pm_ctx* c, const KnnDevU8& B, uint64_t n, const KnnDevU8& Q, uint64_t nq, uint32_t K,
+                         bool self_base, uint32_t* out, float* dist, uint32_t* len) {
+  c->timed("knn_prefilter_u8", (double)nq * n * B.dp, [&] {
+    pmk::knn_i8(c->stream, B.xb.p, B.xc.as<int32_t>(), n, Q.xb.p, Q.xc.as<int32_t>(), nq, B.dp, K, self_base, out, dist,
+                len); });
+}
+
+extern "C" uint32_t pm_knn_u8_max_dim(void) { return pmk::knn_u8_max_dim(); }
+
+extern "C" int pm_knn_u8(pm_ctx* c, const uint8_t* base, uint64_t n, uint64_t dim, const uint8_t* queries, uint64_t nq,
+                         uint32_t k, int64_t* ids, float* dists) {
+  if (!c || !base || (!queries && nq) || (!ids && nq)) return fail(PM_EINVAL, "NULL argument");
+  if (!pmk::knn_u8_pad_dim((uint32_t)std::min<uint64_t>(dim, UINT32_MAX))) return fail(PM_EINVAL, kU8DimText);
+  if (k == 0 || k > pmk::knn_top_k128()) return fail(PM_EINVAL, kK128KText);
+  if (n == 0 || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be in [1, 2^32-1)");
+  HIPCHK(hipSetDevice(c->device));
+  KnnDevU8 B, Q;
+  CHK(knn_upload_u8(c, base, n, (uint32_t)dim, B, false));
+  CHK(knn_upload_u8(c, queries, nq, (uint32_t)dim, Q, false));
+  DevBuf out, dist, len;
+  CHK(out.reserve(std::max<uint64_t>(4, nq * k * 4)));
+  CHK(dist.reserve(std::max<uint64_t>(4, nq * k * 4)));
+  CHK(len.reserve(std::max<uint64_t>(4, nq * 4)));
+  knn_i8_timed(c, B, n, Q, nq, k, false, out.as<uint32_t>(), dist.as<float>(), len.as<uint32_t>());
+  std::vector<uint32_t> o(nq * k), l(nq);
+  std::vector<float> dd(nq * k);
+  HIPCHK(hipMemcpyAsync(o.data(), out.p, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(dd.data(), dist.p, nq * k * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(l.data(), len.p, nq * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (uint64_t i = 0; i < nq; ++i)
+    for (uint32_t j = 0; j < k; ++j) {
+      ids[i * k + j] = j < l[i] ? (int64_t)o[i * k + j] : -1;
+      if (dists) dists[i * k + j] = j < l[i] ? dd[i * k + j] : INFINITY;
+    }
+  return 0;
+}
+
+extern "C" int pm_build_graph_u8(pm_ctx* c, const uint8_t* vectors, uint64_t n, uint64_t dim, uint64_t m, float alpha,
+                                 uint64_t seed, uint32_t* graph, double* times) {
+  if (!c || !vectors || !graph) return fail(PM_EINVAL, "NULL argument");
+  if (!pmk::knn_u8_pad_dim((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)) || dim > pmk::prune_max_dim())
+    return fail(PM_EINVAL, kU8DimText);
+  const uint32_t K = (uint32_t)((float)m * 1.5f);   // int(float32(m)*1.5) NGT results (build_graph.go:398)
+  if (m == 0 || m > pmk::prune_max_m() || K + 1 > pmk::knn_top_k128())
+    return fail(PM_EINVAL, "m must be in [1, 64] (1.5 m candidates + self within the 128-key list)");
+  if (n <= m || n >= (1ull << 32) - 1) return fail(PM_EINVAL, "n must be > m (the random fill needs m other vertices)");
+  KnnDevU8 X;
+  DevBuf out, len;
+  return build_graph_core(
+      c, n, dim, m, alpha, seed, graph, times, false, K,
+      [&] { return knn_upload_u8(c, vectors, n, (uint32_t)dim, X, true); },
+      [&](BuildCand& bc) {
+        CHK(out.reserve(std::max<uint64_t>(4, n * K * 4)));
+        CHK(len.reserve(std::max<uint64_t>(4, n * 4)));
+        knn_i8_timed(c, X, n, X, n, K, true, out.as<uint32_t>(), nullptr, len.as<uint32_t>());
+        bc = {X.xf.as<float>(), out.as<uint32_t>(), len.as<uint32_t>()};
+        return 0;
+      });
 }
 
 // pm_robust_prune and pm_robust_prune_wide: k_prune (wide, rows above kWideFrom:

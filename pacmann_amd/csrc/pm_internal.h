@@ -604,4 +604,14 @@ void knn_rerank_cert_k128(hipStream_t st, const float* X, uint64_t N, uint32_t d
                           uint64_t* nlist, float* eps_out = nullptr);
 void knn_brute_k128(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, const uint64_t* list,
                     uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
+// uint8 rows on the int8 matrix cores (pm_graph_u8.hip; pm_knn_u8, pm_build_graph_u8): u8_bias writes
+// n rows of dp bytes (x ^ 0x80, 0 padded; dp = knn_u8_pad_dim(dim): the next multiple of 64, 0 above
+// knn_u8_max_dim()) and the rows' int32 constants; knn_i8 the first K (K <= 128) of every query
+// row's (integer distance, id) ranking, out / dist [M][K] and len [M] as knn_rerank's.
+uint32_t knn_u8_max_dim();
+uint32_t knn_u8_pad_dim(uint32_t dim);
+void u8_bias(hipStream_t st, const uint8_t* rows, uint64_t n, uint32_t dim, uint32_t dp, void* out, int32_t* cst);
+void u8_to_f32(hipStream_t st, const uint8_t* rows, uint64_t count, float* out);
+void knn_i8(hipStream_t st, const void* X, const int32_t* xc, uint64_t N, const void* Q, const int32_t* qc, uint64_t M,
+            uint32_t dp, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
 }  // namespace pmk

@@ -8,7 +8,8 @@ follow loader.go case by case, including its edge behaviour:
 * ``.bvecs`` (LoadBvecsFile :16-58): records ``<int32 dim><dim x uint8>``; a
   file shorter than ``n`` records leaves the remaining rows zero (the Go code
   prints "Unexpected EOF" and returns what it has); a longer record is cut to
-  ``dim`` (``copy`` semantics).
+  ``dim`` (``copy`` semantics).  ``load_bvecs_u8`` returns the same rows as
+  uint8 (for ``pm.knn_u8`` / ``pm.build_graph_u8``).
 * ``.fvecs`` (LoadFvecsFile :64-84): records ``<int32 dim><dim x float32>``;
   reading stops at the first short record, so fewer than ``n`` rows may come back.
 * ``.ivecs`` (LoadIvecsFile :90-115): records ``<int32 dim><dim x uint32>``; a
@@ -33,7 +34,7 @@ import sys
 
 import numpy as np
 
-__all__ = ["load_float32_matrix", "load_bvecs", "load_fvecs", "load_ivecs", "load_txt_float32",
+__all__ = ["load_float32_matrix", "load_bvecs", "load_bvecs_u8", "load_fvecs", "load_ivecs", "load_txt_float32",
            "load_npy_float32", "load_graph", "load_graph_npy", "load_graph_txt", "save_graph",
            "save_graph_npy", "save_graph_txt", "load_int_matrix", "save_int_matrix_file"]
 
@@ -97,6 +98,30 @@ def _body(raw: np.ndarray, rows: int, d: int, item: int) -> np.ndarray:
 def load_bvecs(path, n: int, dim: int) -> np.ndarray:
     raw = _map(path)
     out = np.zeros((n, dim), dtype=np.float32)
+    u = _uniform_prefix(raw, 1, n)
+    if u is not None:
+        rows, d = u
+        w = min(d, dim)
+        out[:rows, :w] = _body(raw, rows, d, 1)[:, :w]
+        if rows < n:
+            print("Unexpected EOF", file=sys.stderr)
+        return out
+    i = 0
+    for d, payload in _records(raw, 1, n):
+        w = min(d, dim)
+        out[i, :w] = payload[:w]
+        i += 1
+    if i < n:
+        print("Unexpected EOF", file=sys.stderr)
+    return out
+
+
+def load_bvecs_u8(path, n: int, dim: int) -> np.ndarray:
+    """load_bvecs without the float32 expansion: the same records, truncation,
+    zero fill and "Unexpected EOF", as an (n, dim) uint8 array (a quarter of the
+    memory), the input of pm.knn_u8 and pm.build_graph_u8."""
+    raw = _map(path)
+    out = np.zeros((n, dim), dtype=np.uint8)
     u = _uniform_prefix(raw, 1, n)
     if u is not None:
         rows, d = u
