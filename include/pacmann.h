@@ -67,7 +67,10 @@ int         pm_ctx_mem_info(pm_ctx* ctx, uint64_t* free_bytes, uint64_t* total_b
  * bench: a sample, at a fraction of the events' cost).  Host wall-clock
  * accumulators are always on: "host_step_launch", "host_step_wait",
  * "host_step_post", "host_batch_query", "host_gvi_parse", "host_search_knn",
- * "host_knn_init", "host_knn_batch", "host_knn_update", "host_knn_final".
+ * "host_knn_init", "host_knn_batch", "host_knn_update", "host_knn_final";
+ * "host_gvi_group" (the wall time of pm_graph_group_get_vertex_info, one entry
+ * per call that fetched anything) and "host_gvi_group_steps" (the shared steps
+ * those calls launched: a count, total_ms 0), both on sessions[0]'s context.
  * So are the step-form counters, one launch count per kernel form as the
  * step's plan launched it (total_ms 0 unless noted), on the
  * context whose stream ran the step: "host_path_match", "host_path_match_part",
@@ -406,6 +409,7 @@ pm_batchpir* pm_graph_pir(pm_graph* g);
  *   pm_graph_get_metadata     GetMetadata()      private-search.go (n, dim, m)
  *   pm_graph_get_vertex_info  GetVertexInfo(ids) private-search.go:441-506
  *   pm_graph_get_start_vertex GetStartVertex()   private-search.go:508-531
+ *   pm_graph_group_*          GetVertexInfo / Preprocess of many sessions at once
  * pm_graph_get_vertex_info fetches every id through the batch PIR
  * (SimpleBatchPianoPIR.Query, one call per batch) and decodes the entries
  * (Entry2VectorAndNeighbors, :418-439) into vecs (n x dim f32) and nbrs
@@ -422,6 +426,44 @@ int pm_graph_get_vertex_info(pm_graph* g, const uint64_t* ids, uint64_t n, float
                              const float* query, float* dist);
 int pm_graph_get_start_vertex(pm_graph* g, uint64_t cap, uint64_t* ids, float* vecs, uint32_t* nbrs,
                               uint64_t* count);
+/* Many sessions' GetVertexInfo calls answered together: what
+ * pm_batchpir_group_query is to SimpleBatchPianoPIR.Query, for a server whose
+ * clients keep their own beam search.  Sessions: private, preprocessed,
+ * unsharded clients of one server DB on one device with distinct contexts (a
+ * base and its pm_graph_create_session handles, as pm_search_loop_batched
+ * takes); PM_EINVAL with a message, before any HIP call, for a NULL, repeated,
+ * non-private, sharded, lost or not preprocessed session and for sessions of
+ * different devices or servers.  The group keeps the handles, which must
+ * outlive it; its shared steps run on sessions[0]'s stream.  A session may be
+ * used alone between group calls (never concurrently with one), and may be
+ * re-preprocessed with pm_graph_preprocess: the next group call picks up its
+ * new client.
+ * pm_graph_group_get_vertex_info is, for every session s, exactly
+ * pm_graph_get_vertex_info(sessions[s], ids + offs[s], offs[s+1] - offs[s],
+ * ..., queries + s*dim, ...): the same vecs, nbrs, ok and dist at offs[s] (rows
+ * of dim / m / 1 / 1 elements per id), the same pm_graph_counts, batch-PIR
+ * statistics and hint state afterwards, bit for bit.  As there, a session's
+ * ids are ONE SimpleBatchPianoPIR.Query; the sub-queries of all sessions go
+ * into ONE shared step, with every row scored against its own session's query
+ * (the S queries go to the device in one copy per call).  A session with
+ * offs[s] == offs[s+1] sits the call out untouched.  A session whose bucketing
+ * leaves the one-step path (a partition at its query budget, fewer ids than
+ * partitions, more than 256 sub-queries per partition) is served alone in that
+ * call, as pm_graph_get_vertex_info serves it, and the others still share the
+ * step.  Any output may be NULL; dist needs queries (S x dim, or NULL).  offs
+ * (S + 1 entries) must not descend; an id >= n of any session fails the whole
+ * call (PM_EINVAL) before any session's state moves.
+ * pm_graph_group_preprocess is pm_graph_preprocess of every session, the hint
+ * folds of the sessions that are clients of a base as ONE launch set (as
+ * pm_batchpir_group_preprocessing); every session's state equals that of its
+ * own pm_graph_preprocess. */
+typedef struct pm_graph_group pm_graph_group;
+int  pm_graph_group_create(pm_graph** sessions, uint32_t S, pm_graph_group** out);
+void pm_graph_group_destroy(pm_graph_group* gg);
+int  pm_graph_group_get_vertex_info(pm_graph_group* gg, const uint64_t* ids, const uint64_t* offs /* S+1 */,
+                                    float* vecs, uint32_t* nbrs, uint8_t* ok,
+                                    const float* queries /* S x dim or NULL */, float* dist);
+int  pm_graph_group_preprocess(pm_graph_group* gg);
 
 /* ---- private search over a SHARDED graph DB (multi-GPU) --
  * The reference's PIRGraphInfo (private-search.go:336-531) fetches every

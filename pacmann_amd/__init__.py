@@ -21,7 +21,7 @@ import numpy as np
 __all__ = [
     "Context", "PianoPIR", "SimpleBatchPianoPIR", "PIRGraphInfo", "GraphANNFrontend",
     "lib", "expand_key", "prf_batch", "l2_batch", "ip_batch", "ip_bench", "LIB_PATH",
-    "QueryError",
+    "QueryError", "PIRGraphGroup",
 ]
 
 import os as _os
@@ -175,6 +175,10 @@ SIGNATURES = {
     "pm_graph_get_metadata": (C.c_int, [vp, u64p, u64p, u64p]),
     "pm_graph_get_vertex_info": (C.c_int, [vp, u64p, u64, f32p, u32p, u8p, f32p, f32p]),
     "pm_graph_get_start_vertex": (C.c_int, [vp, u64, u64p, f32p, u32p, u64p]),
+    "pm_graph_group_create": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
+    "pm_graph_group_destroy": (None, [vp]),
+    "pm_graph_group_get_vertex_info": (C.c_int, [vp, u64p, u64p, f32p, u32p, u8p, f32p, f32p]),
+    "pm_graph_group_preprocess": (C.c_int, [vp]),
     "pm_rccl_unique_id": (C.c_int, [u8p]),
     "pm_rccl_create": (C.c_int, [C.c_int, C.c_int, C.c_int, u8p, C.c_uint32, C.POINTER(vp)]),
     "pm_rccl_destroy": (None, [vp]),
@@ -831,6 +835,66 @@ class PIRGraphInfo:
         _check(lib().pm_graph_create_session(s.ctx.h, self.h, pir_seed, search_seed, C.byref(h)))
         s.h = h
         return s
+
+
+class PIRGraphGroup:
+    """Private sessions of one server DB whose GetVertexInfo calls are answered
+    together (pm_graph_group_*): for every session exactly its own
+    PIRGraphInfo.GetVertexInfo, with all sessions' sub-queries in one shared
+    step.  sessions: preprocessed PIRGraphInfo objects (a base and its
+    Session()s), kept alive while the group exists."""
+
+    def __init__(self, sessions):
+        self.sessions = list(sessions)
+        hs = (vp * len(self.sessions))(*[s.h for s in self.sessions])
+        h = vp()
+        _check(lib().pm_graph_group_create(hs, len(self.sessions), C.byref(h)))
+        self.h = h
+        self.Dim, self.M = self.sessions[0].Dim, self.sessions[0].M
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().pm_graph_group_destroy(self.h)
+        self.h = None
+
+    def preprocess(self):
+        """Every session's Preprocess(), the hint folds as one launch set."""
+        _check(lib().pm_graph_group_preprocess(self.h))
+
+    def get_vertex_info(self, ids_per_session, queries=None, want=("vecs", "nbrs", "ok", "dist")):
+        """ids_per_session: one sequence of vertex ids per session (empty: the
+        session sits the call out); queries [S, dim] or None.  Returns one
+        (vecs [n_s, dim] f32, nbrs [n_s, m] u32, ok [n_s] bool, dist [n_s] f32 or
+        None) per session.  want: the outputs to fetch (the others are passed
+        as NULL and returned as None)."""
+        S = len(self.sessions)
+        if len(ids_per_session) != S:
+            raise ValueError("one sequence of ids per session")
+        per = [_u64(i).ravel() for i in ids_per_session]
+        offs = np.zeros(S + 1, dtype=np.uint64)
+        offs[1:] = np.cumsum([len(i) for i in per])
+        n = int(offs[-1])
+        ids = np.ascontiguousarray(np.concatenate(per)) if n else np.zeros(1, dtype=np.uint64)
+        q = None
+        if queries is not None:
+            q = np.ascontiguousarray(queries, dtype=np.float32)
+            if q.shape != (S, self.Dim):
+                raise ValueError("queries must be [len(sessions), dim]")
+        vec = np.zeros((n, self.Dim), dtype=np.float32) if "vecs" in want else None
+        nb = np.zeros((n, self.M), dtype=np.uint32) if "nbrs" in want else None
+        ok = np.zeros(n, dtype=np.uint8) if "ok" in want else None
+        d = np.zeros(n, dtype=np.float32) if q is not None and "dist" in want else None
+
+        def ptr(a, t):
+            return None if a is None else _p(a, t)
+        _check(lib().pm_graph_group_get_vertex_info(self.h, _p(ids, u64p), _p(offs, u64p), ptr(vec, f32p), ptr(nb, u32p),
+                                                    ptr(ok, u8p), ptr(q, f32p), ptr(d, f32p)))
+        out = []
+        for s in range(S):
+            a, b = int(offs[s]), int(offs[s + 1])
+            out.append((None if vec is None else vec[a:b], None if nb is None else nb[a:b],
+                        None if ok is None else ok[a:b].astype(bool), None if d is None else d[a:b]))
+        return out
 
 
 def search_loop_sessions(sessions, queries, k: int, step: int, parallel: int):

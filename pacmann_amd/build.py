@@ -23,7 +23,7 @@ SOURCES = [CSRC / "pm_kernels.hip", CSRC / "pm_query.hip", CSRC / "pm_graph.hip"
            CSRC / "pm_search.cpp", CSRC / "pm_group.cpp", CSRC / "pm_devloop.cpp",
            CSRC / "pm_rccl.cpp", CSRC / "pm_build.cpp"]
 HEADERS = [CSRC / "pm_internal.h", CSRC / "pm_search_dev.h", CSRC / "pm_aes.h", CSRC / "pm_aes_bs.h",
-           CSRC / "pm_host.h", CSRC / "pm_engine.h", CSRC / "pm_graph_dev.h", ROOT / "include" / "pacmann.h"]
+           CSRC / "pm_host.h", CSRC / "pm_engine.h", CSRC / "pm_gvi_offs.h", CSRC / "pm_graph_dev.h", ROOT / "include" / "pacmann.h"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [

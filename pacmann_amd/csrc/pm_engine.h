@@ -53,6 +53,7 @@ int batch_query_impl(Engine* g, const uint64_t* idx, uint64_t n, uint64_t* out, 
                      uint32_t dim, float* dist_out, const uint64_t** rows_out, uint8_t* ok);
 // pm_search.cpp
 int check_session(const pm_graph* g);
+int graph_start_set(pm_graph* g);
 int gvi_pre(pm_graph* g, bool with_q, bool* fast);
 int gvi_post(pm_graph* g, bool with_q, bool fast);
 void knn_reset(pm_graph* g);
@@ -203,6 +204,10 @@ struct PartHost {
 
 struct Engine {
   pm_ctx* ctx = nullptr;
+  // a serial number per process: pm_graph_preprocess re-creates a session's client, possibly at the same
+  // address, and a pm_graph_group that copied the old one's parts must notice
+  static uint64_t next_uid() { static std::atomic<uint64_t> n{0}; return ++n; }
+  const uint64_t uid = next_uid();
   bool is_batch = false;
   uint64_t N = 0, E = 0, Ebytes = 0, F = 0, seed = 0;
   uint64_t B = 0, P = 1, PS = 0;

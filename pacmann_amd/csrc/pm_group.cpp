@@ -4,6 +4,7 @@
 // and pm_search_loop_sharded.  Needs pm_ctx.cpp, pm_engine.cpp and
 // pm_search.cpp.
 #include "pm_engine.h"
+#include "pm_gvi_offs.h"
 
 // ---------------------------------------------------------------------------
 // Batched multi-session serving: S client sessions in
@@ -955,6 +956,213 @@ extern "C" int pm_batchpir_group_query(pm_batchpir_group* h, const uint64_t* ids
     CHK(bq_tail(e, n));
   }
   return 0;
+}
+
+// ---- GetVertexInfo of many graph sessions served together (the plugin API) --
+// S private sessions of one server DB (pm_graph_create_session): every
+// pm_graph_group_get_vertex_info call makes, for each session s, exactly the
+// pm_graph_get_vertex_info call of its own ids and query (GetVertexInfo,
+// private-search.go:441-506: ONE SimpleBatchPianoPIR.Query of all its ids, the
+// decode, the success count), with all sessions' sub-queries in ONE shared
+// step on sessions[0]'s stream and each row scored against its own session's
+// query (PmPart::qv pointing into the group's query buffer).  A session whose
+// bucketing leaves the one-step path (a partition at its query budget, fewer
+// ids than partitions, more than step_max_sub_per_part() per partition) is
+// served alone by batch_query_impl, as pm_graph_get_vertex_info serves it.
+// The rows come back whole (rows_partial = false: the caller reads the vectors
+// too) in the step's pinned result buffer and the distances and statuses in
+// its headers, so the call adds one copy to the step: the S queries, up.
+struct pm_graph_group {
+  StepGroup G;
+  std::vector<pm_graph*> gs;
+  std::vector<uint64_t> uid;   // Engine::uid of each session's client when its parts were copied
+  std::vector<char> fast;
+  std::vector<uint8_t> okv;
+  std::vector<float> dv;
+};
+// A session re-preprocessed by pm_graph_preprocess has a new client: its parts replace the old one's.
+static int gvi_group_refresh(pm_graph_group* h) {
+  StepGroup& G = h->G;
+  bool changed = false;
+  for (uint32_t s = 0; s < G.S; ++s) {
+    pm_graph* g = h->gs[s];
+    CHK(check_session(g));
+    if (!g->pir) return fail(PM_EINVAL, "session " + std::to_string(s) + " is not preprocessed");
+    Engine* e = &g->pir->e;
+    if (e->uid == h->uid[s]) continue;
+    if (e->P != G.P || e->E != G.E || e->maxPH != G.maxPH || e->maxSS != G.maxSS || e->nshards != 1)
+      return fail(PM_EINVAL, "session " + std::to_string(s) + " is no longer a client of the group's server DB");
+    G.es[s] = e;
+    h->uid[s] = e->uid;
+    changed = true;
+  }
+  if (changed) CHK(group_upload_parts(G));
+  return 0;
+}
+// Entry2VectorAndNeighbors (private-search.go:418-439) + the success count (:483-497) of session g's n ids
+static void gvi_group_decode(pm_graph* g, const uint64_t* ids, uint64_t n, const uint8_t* okv, const float* dv,
+                             float* vecs, uint32_t* nbrs, uint8_t* ok, float* dist) {
+  const uint64_t dim = g->dim, m = g->m;
+  uint32_t tmp[64];
+  for (uint64_t i = 0; i < n; ++i) {
+    const char* r = (const char*)g->rowp[i];
+    if (vecs) memcpy(vecs + i * dim, r, dim * 4);
+    if (nbrs) memcpy(nbrs + i * m, r + dim * 4, m * 4);
+    if (memcmp(r + dim * 4, g->true_nb(ids[i], tmp), m * 4) == 0) g->succ++;
+    if (ok) ok[i] = okv[i];
+    if (dist) dist[i] = dv[i];
+  }
+}
+extern "C" int pm_graph_group_create(pm_graph** sessions, uint32_t S, pm_graph_group** out) {
+  if (!sessions || !S || !out) return fail(PM_EINVAL, "NULL argument");
+  for (uint32_t i = 0; i < S; ++i) {   // by address first: nothing is read through a pointer given twice
+    if (!sessions[i]) return fail(PM_EINVAL, "NULL session");
+    for (uint32_t j = 0; j < i; ++j)
+      if (sessions[j] == sessions[i]) return fail(PM_EINVAL, "a session appears twice");
+  }
+  for (uint32_t i = 0; i < S; ++i) {
+    const pm_graph* g = sessions[i];
+    const std::string who = "session " + std::to_string(i);
+    if (g->nonprivate) return fail(PM_EINVAL, who + " is not private: a group fetches through the batch PIR");
+    if (g->nshards > 1) return fail(PM_EINVAL, who + " is sharded: a sharded graph searches through pm_search_loop_sharded");
+    if (!g->lost.empty()) return fail(PM_EINVAL, who + ": session state lost: " + g->lost);
+    if (!g->pir) return fail(PM_EINVAL, who + " is not preprocessed");
+    if (g->ctx->device != sessions[0]->ctx->device) return fail(PM_EINVAL, "grouped sessions must be on one device");
+    const Engine& a = sessions[0]->pir->e;
+    const Engine& b = g->pir->e;
+    if (a.db.get() != b.db.get() || a.P != b.P || a.E != b.E || a.N != b.N || g->n != sessions[0]->n ||
+        g->dim != sessions[0]->dim || g->m != sessions[0]->m || b.nshards != 1 || !b.is_batch)
+      return fail(PM_EINVAL, "grouped sessions must be clients of one server DB");
+    for (uint32_t j = 0; j < i; ++j)
+      if (sessions[j]->ctx == g->ctx) return fail(PM_EINVAL, "grouped sessions need distinct contexts");
+  }
+  pm_graph_group* h = new pm_graph_group();
+  StepGroup& G = h->G;
+  h->gs.assign(sessions, sessions + S);
+  h->fast.assign(S, 0);
+  G.dim = (uint32_t)sessions[0]->dim;
+  G.rows_partial = false;   // whole rows: the caller reads the vectors too
+  auto init = [&]() -> int {
+    HIPCHK(hipSetDevice(sessions[0]->ctx->device));
+    for (uint32_t i = 0; i < S; ++i) HIPCHK(hipStreamSynchronize(sessions[i]->ctx->stream));
+    const uint64_t qbytes = (uint64_t)S * G.dim * 4;
+    CHK(G.qbuf.reserve(qbytes));
+    CHK(G.qstage.reserve(qbytes));
+    HIPCHK(hipMemset(G.qbuf.p, 0, qbytes));   // the rows of a call without queries are scored against zeros, unread
+    for (uint32_t i = 0; i < S; ++i) {
+      G.es.push_back(&sessions[i]->pir->e);
+      h->uid.push_back(sessions[i]->pir->e.uid);
+      G.qv.push_back(G.qbuf.as<float>() + (uint64_t)i * G.dim);
+    }
+    return group_init(G, sessions[0]->ctx);
+  };
+  if (int r = init()) { delete h; return r; }
+  *out = h;
+  return 0;
+}
+extern "C" void pm_graph_group_destroy(pm_graph_group* h) { delete h; }
+
+extern "C" int pm_graph_group_get_vertex_info(pm_graph_group* h, const uint64_t* ids, const uint64_t* offs, float* vecs,
+                                              uint32_t* nbrs, uint8_t* ok, const float* queries, float* dist) {
+  if (dist && !queries) return fail(PM_EINVAL, "dist needs the queries");
+  if (!h || !offs) return fail(PM_EINVAL, "NULL argument");
+  StepGroup& G = h->G;
+  const uint32_t S = G.S;
+  uint32_t live = 0, bad_s = 0;
+  uint64_t max_n = 0, end = 0, bad_i = 0;
+  if (pmgvi::walk(offs, S, &live, &max_n, &end, &bad_s) != pmgvi::OFFS_OK)
+    return fail(PM_EINVAL, "offs descends at session " + std::to_string(bad_s));
+  if (live && !ids) return fail(PM_EINVAL, "NULL argument");
+  // every refusal comes before any session's state moves
+  for (uint32_t s = 0; s < S; ++s) {
+    CHK(check_session(h->gs[s]));
+    if (!h->gs[s]->pir) return fail(PM_EINVAL, "session " + std::to_string(s) + " is not preprocessed");
+  }
+  if (pmgvi::check_ids(ids, offs, S, h->gs[0]->n, &bad_s, &bad_i) != pmgvi::OFFS_OK)
+    return fail(PM_EINVAL, "session " + std::to_string(bad_s) + ": vertex id " + std::to_string(ids[bad_i]) + " out of range");
+  if (!live) return 0;
+  auto t_call = Clock::now();
+  pm_ctx* c = G.c;
+  HIPCHK(hipSetDevice(c->device));
+  CHK(gvi_group_refresh(h));
+  const uint64_t dim = G.dim, m = h->gs[0]->m;
+  if (queries) {   // all sessions' queries in one copy, ahead of the step on its stream
+    memcpy(G.qstage.p, queries, (uint64_t)S * dim * 4);
+    HIPCHK(hipMemcpyAsync(G.qbuf.p, G.qstage.p, (uint64_t)S * dim * 4, hipMemcpyHostToDevice, c->stream));
+  }
+  h->okv.resize(max_n);
+  h->dv.resize(max_n);
+  bool q_landed = !queries;   // a session served alone reads its query on its own stream
+  for (uint32_t s = 0; s < S; ++s) {   // bucketing; sessions off the one-step path go alone, now
+    const pmgvi::Slice sl = pmgvi::slice(offs, s);
+    h->fast[s] = 0;
+    if (!sl.n) continue;   // sits the call out
+    pm_graph* g = h->gs[s];
+    Engine* e = G.es[s];
+    const uint64_t* sid = ids + sl.off;
+    g->total += sl.n;   // totalQueryNum (:443)
+    g->rowp.resize(sl.n);
+    e->rows_partial = false;
+    bool f = false;
+    CHK(bq_prepare(e, sid, sl.n, &f));
+    h->fast[s] = f;
+    if (f) continue;
+    if (!q_landed) { HIPCHK(hipStreamSynchronize(c->stream)); q_landed = true; }
+    CHK(batch_query_impl(e, sid, sl.n, nullptr, queries ? G.qv[s] : nullptr, (uint32_t)dim, queries ? h->dv.data() : nullptr,
+                         g->rowp.data(), h->okv.data()));
+    gvi_group_decode(g, sid, sl.n, h->okv.data(), h->dv.data(), vecs ? vecs + sl.off * dim : nullptr,
+                     nbrs ? nbrs + sl.off * m : nullptr, ok ? ok + sl.off : nullptr, dist ? dist + sl.off : nullptr);
+  }
+  if (pmgvi::shared_steps(h->fast.data(), S)) {
+    CHK(group_step(G, h->fast));
+    c->host_add(HT_GVI_GROUP_STEPS, 0.0);
+    for (uint32_t s = 0; s < S; ++s) {
+      if (!h->fast[s]) continue;
+      const pmgvi::Slice sl = pmgvi::slice(offs, s);
+      pm_graph* g = h->gs[s];
+      Engine* e = G.es[s];
+      const uint64_t* sid = ids + sl.off;
+      CHK(group_collect(G, s));
+      bq_emit_fast(e, sid, sl.n, nullptr, h->dv.data(), g->rowp.data(), h->okv.data());
+      CHK(bq_tail(e, sl.n));
+      gvi_group_decode(g, sid, sl.n, h->okv.data(), h->dv.data(), vecs ? vecs + sl.off * dim : nullptr,
+                       nbrs ? nbrs + sl.off * m : nullptr, ok ? ok + sl.off : nullptr, dist ? dist + sl.off : nullptr);
+    }
+  }
+  c->host_add(HT_GVI_GROUP, ms_since(t_call));
+  return 0;
+}
+
+// pm_graph_preprocess (PIRGraphInfo.Preprocess, private-search.go:355-412, then
+// GetStartVertex, :508-531) of every session: the sessions that are clients of
+// a base get their new clients first and are folded as ONE launch set
+// (prep_clients, as pm_batchpir_group_preprocessing); a base, which packs and
+// uploads its own server DB, and DummyPreprocessing sessions go through
+// pm_graph_preprocess itself.
+extern "C" int pm_graph_group_preprocess(pm_graph_group* h) {
+  if (!h) return fail(PM_EINVAL, "NULL argument");
+  StepGroup& G = h->G;
+  for (uint32_t s = 0; s < G.S; ++s) CHK(check_session(h->gs[s]));
+  HIPCHK(hipSetDevice(G.c->device));
+  std::vector<Engine*> who;
+  std::vector<pm_graph*> folded, alone;
+  for (pm_graph* g : h->gs) {
+    if (!g->server || g->skipPrep) { alone.push_back(g); continue; }
+    delete g->pir; g->pir = nullptr;
+    CHK(pm_batchpir_create_client(g->ctx, g->server, g->pir_seed, &g->pir));
+    who.push_back(&g->pir->e);
+    folded.push_back(g);
+  }
+  CHK(prep_clients(G.c, G.prep_parts, G.lp, who, nullptr));
+  for (pm_graph* g : folded) CHK(graph_start_set(g));
+  for (pm_graph* g : alone) {
+    const pm_batchpir* old = g->pir;
+    CHK(pm_graph_preprocess(g));
+    if (!g->server)   // a base: the group's sessions follow it to its new server
+      for (pm_graph* x : h->gs)
+        if (x->server == old) x->server = g->pir;
+  }
+  return gvi_group_refresh(h);
 }
 
 // pm_search_loop_batched with the host work pooled (the default; PM_BATCH_POOL=0:

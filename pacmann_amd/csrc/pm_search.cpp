@@ -161,6 +161,11 @@ extern "C" int pm_graph_preprocess(pm_graph* g) {
     if (g->skipPrep) CHK(pm_batchpir_dummy_preprocessing(g->pir));
     else CHK(pm_batchpir_preprocessing(g->pir));
   }
+  return graph_start_set(g);
+}
+// GetStartVertex (private-search.go:508-531): the second half of pm_graph_preprocess, on its own for
+// pm_graph_group_preprocess, which folds the sessions' hints as one launch set first.
+int pmh::graph_start_set(pm_graph* g) {
   const uint64_t target = (uint64_t)std::sqrt((double)g->n);
   std::unordered_map<uint64_t, bool> added;
   g->start.clear();
