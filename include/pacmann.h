@@ -714,6 +714,90 @@ int pm_build_graph_u8(pm_ctx* ctx, const uint8_t* vectors, uint64_t n, uint64_t 
                       uint64_t seed, uint32_t* graph, double* times);
 uint32_t pm_knn_u8_max_dim(void);   /* 256 */
 
+/* ---- k-means and the cluster-search baseline ---------- */
+/* Deterministic Lloyd iterations (the clustering() of the reference's
+ * cluster-search.py:88-107, which calls faiss.Kmeans(niter=20) and then
+ * index.search(vectors, 1)).  dim in [1, 1024] ("dim must be in [1, 1024]"),
+ * n in [1, 2^32-1) ("n must be in [1, 2^32-1)"), nc in [1, n] ("nc must be in
+ * [1, n]"), niter in [0, 10000] ("niter must be in [0, 10000]"); ctx, vectors,
+ * centroids and labels not NULL; all checked before any HIP call.
+ *
+ * Start: init [nc][dim] as given, or, when it is NULL, centroid c = row pick[c],
+ * pick the first nc entries of a Fisher-Yates shuffle of 0 .. n-1 whose i-th
+ * swap partner is i + hash4(seed, 12, i, 0, 0) % (n - i) (O(nc) host memory).
+ * This is not faiss's sampling: the reference seeds faiss from its own RNG and
+ * is not reproducible between runs anyway; faiss's empty-cluster splitting and
+ * its sub-sampling of the training points are not done either.
+ *
+ * Assignment: labels[i] = the c that minimises (L2Dist(row i, centroid c), c),
+ * L2Dist in l2_distance_amd64.s order, ties to the lowest c, exact for every
+ * finite input: pm_knn_k128's device path with the centroids as base, the rows
+ * as queries and k = 1 (timing names as pm_knn_k128's).  The rows' bf16 halves
+ * and norms are made once per call, the centroids' each iteration.
+ *
+ * Update: centroid c becomes the mean of its members, or keeps its value when it
+ * has none.  Coordinate j of the mean: the members in ascending id order; partial
+ * sum p of 16 adds members p, p + 16, ... in that order in f64 from +0.0; the
+ * total is partial 0 plus partials 1 .. 15 in that order; total / size in f64,
+ * rounded once to f32.  This order is part of the contract: the result is a
+ * function of the input alone (no floating-point atomics, nothing that depends
+ * on scheduling), and two calls return the same bits.
+ *
+ * Loop: assign; then niter times: update, assign.  labels is always the
+ * assignment to the returned centroids.  moved [niter + 1] (or NULL): moved[t] =
+ * the rows whose label changed in assignment t, moved[0] = n; when an assignment
+ * moves nothing the loop stops (the centroids are a fixed point) and the
+ * remaining entries are 0.  sizes [nc] (or NULL): the final member counts.
+ * niter = 0 labels the rows by the given centroids.
+ *
+ * Device memory at the peak: n (4 dim + 4 dp + 12) bytes for the rows, their two
+ * bf16 halves (dp: dim padded as pm_knn_k128 pads it), norms and two label
+ * arrays; 20 n bytes plus rocPRIM's sort scratch (about 16 n) for the member
+ * lists; nc (4 dim + 4 dp + 4) for the centroids; and about 540 bytes per row of
+ * an assignment chunk of at most 262,144 rows (142 MB), whatever n is.  Timing
+ * names of the stages that are not the kNN's: "kmeans_sort" (the member lists),
+ * "kmeans_update", "kmeans_moved". */
+int pm_kmeans(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, uint64_t nc, uint32_t niter,
+              uint64_t seed, const float* init /* nc x dim or NULL */, float* centroids /* nc x dim */,
+              uint32_t* labels /* n */, uint64_t* sizes /* nc or NULL */, uint64_t* moved /* niter + 1 or NULL */);
+
+/* The cluster-ordered index of cluster-search.py (cluster_search_index,
+ * :110-198) on the device.  pm_cluster_create takes centroids [nc][dim] and
+ * labels [n] from anywhere (pm_kmeans, or the reference's saved -centroids.npy /
+ * -labels.npy); dim and n as pm_kmeans, nc in [1, 2^32-1), a label >= nc is
+ * PM_EINVAL ("label out of range"), all before any HIP call.  It keeps on the
+ * device the rows gathered into cluster order (sorted_vectors, :122-131; within a
+ * cluster by ascending id; "cluster_sort", "cluster_gather"), order [n] (the
+ * original id of every position), and the centroids with their bf16 halves;
+ * offsets [nc + 1] and a copy of order stay on the host (pm_cluster_info; any
+ * output may be NULL).  Device memory held: n (4 dim + 4) + nc (4 dim + 4 dp + 4)
+ * bytes; twice the rows during the create.  The context must outlive the index.
+ *
+ * pm_cluster_search: k in [1, 128] ("k must be in [1, 128]"), nq >= 1 ("nq must
+ * be > 0"), nprobe in [1, min(nc, 128)] ("nprobe must be in [1, min(nc, 128)]").
+ * probed [nq][nprobe] (or NULL) = the nprobe nearest centroids of each query by
+ * (L2Dist, c), exact (pm_knn_k128's device path).  ids [nq][k] = the k smallest
+ * (L2Dist(row, query), original id) keys over the union of the probed clusters'
+ * rows, dists [nq][k] (or NULL) their distances, -1 / +inf padded as the kNN
+ * calls'; scanned [nq] (or NULL) = the rows scored (the sum of the probed
+ * sizes).  Timing names: "cluster_scan" and "cluster_merge", once per 65,536
+ * queries, beside the kNN's.
+ *
+ * Departures from the script: distances are the graph side's squared L2Dist (the
+ * script's np.linalg.norm gives the same ranking, not the same bits); ties break
+ * by id (the script's argsort is unstable); a cluster shorter than k pads with
+ * -1 (the script repeats the cluster's first row); nprobe > 1 is an extension
+ * (Tiptoe's search is nprobe = 1). */
+typedef struct pm_cluster pm_cluster;
+int pm_cluster_create(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim, const float* centroids,
+                      uint64_t nc, const uint32_t* labels, pm_cluster** out);
+void pm_cluster_destroy(pm_cluster* h);
+int pm_cluster_info(pm_cluster* h, uint64_t* n, uint64_t* dim, uint64_t* nc, uint64_t* offsets /* nc + 1 or NULL */,
+                    uint32_t* order /* n or NULL */);
+int pm_cluster_search(pm_cluster* h, const float* queries, uint64_t nq, uint32_t k, uint32_t nprobe,
+                      int64_t* ids /* nq x k */, float* dists /* nq x k or NULL */,
+                      uint32_t* probed /* nq x nprobe or NULL */, uint64_t* scanned /* nq or NULL */);
+
 #ifdef __cplusplus
 }
 #endif

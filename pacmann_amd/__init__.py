@@ -21,7 +21,7 @@ import numpy as np
 __all__ = [
     "Context", "PianoPIR", "SimpleBatchPianoPIR", "PIRGraphInfo", "GraphANNFrontend",
     "lib", "expand_key", "prf_batch", "l2_batch", "ip_batch", "ip_bench", "LIB_PATH",
-    "QueryError", "PIRGraphGroup",
+    "QueryError", "PIRGraphGroup", "kmeans", "ClusterIndex",
 ]
 
 import os as _os
@@ -156,6 +156,11 @@ SIGNATURES = {
     "pm_knn_u8": (C.c_int, [vp, u8p, u64, u64, u8p, u64, C.c_uint32, i64p, f32p]),
     "pm_build_graph_u8": (C.c_int, [vp, u8p, u64, u64, u64, C.c_float, u64, u32p, C.POINTER(dbl)]),
     "pm_knn_u8_max_dim": (C.c_uint32, []),
+    "pm_kmeans": (C.c_int, [vp, f32p, u64, u64, u64, C.c_uint32, u64, f32p, f32p, u32p, u64p, u64p]),
+    "pm_cluster_create": (C.c_int, [vp, f32p, u64, u64, f32p, u64, u32p, C.POINTER(vp)]),
+    "pm_cluster_destroy": (None, [vp]),
+    "pm_cluster_info": (C.c_int, [vp, u64p, u64p, u64p, u64p, u32p]),
+    "pm_cluster_search": (C.c_int, [vp, f32p, u64, C.c_uint32, C.c_uint32, i64p, f32p, u32p, u64p]),
     "pm_search_loop_sessions": (C.c_int, [C.POINTER(vp), C.c_uint32, f32p, u64, C.c_int, C.c_int, C.c_int,
                                           i64p, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "pm_batchpir_group_create": (C.c_int, [C.POINTER(vp), C.c_uint32, C.POINTER(vp)]),
@@ -1180,6 +1185,108 @@ def build_graph(vectors, m: int, alpha: float = 1.2, seed: int = 1, ctx: Context
     if exact:
         times["knn_fallback_rows"] = int(fb.value)
     return g, times
+
+
+def kmeans(vectors, nc: int, niter: int = 20, seed: int = 1, init=None, ctx: Context | None = None):
+    """Deterministic Lloyd iterations (pm_kmeans): exact nearest-centroid
+    assignment by (L2Dist, c) and a centroid update in a fixed f64 summation
+    order, so two calls return the same bits.  Without init the start is nc rows
+    picked by hash4(seed, 12, ...).  Returns (centroids [nc, dim] float32, labels
+    [n] uint32, sizes [nc] uint64, moved [niter + 1] uint64: rows that changed
+    label in each assignment, 0 after an early stop)."""
+    ctx = ctx or default_context()
+    v = np.ascontiguousarray(vectors, dtype=np.float32)
+    n, dim = v.shape
+    ip = None
+    if init is not None:
+        i = np.ascontiguousarray(init, dtype=np.float32)
+        if i.shape != (nc, dim):
+            raise ValueError(f"init must be [{nc}, {dim}], got {i.shape}")
+        ip = _p(i, f32p)
+    cen = np.zeros((max(nc, 0), dim), dtype=np.float32)
+    labels = np.zeros(n, dtype=np.uint32)
+    sizes = np.zeros(max(nc, 0), dtype=np.uint64)
+    moved = np.zeros(max(niter, 0) + 1, dtype=np.uint64)
+    _check(lib().pm_kmeans(ctx.h, _p(v, f32p), n, dim, nc, niter, seed, ip, _p(cen, f32p), _p(labels, u32p),
+                           _p(sizes, u64p), _p(moved, u64p)))
+    return cen, labels, sizes, moved
+
+
+class ClusterIndex:
+    """The reference's cluster_search_index (cluster-search.py:110-198) on the
+    GPU (pm_cluster_*): the rows in cluster order on the device, a query scored
+    against the rows of its nprobe nearest centroids' clusters.  centroids and
+    labels come from pm.kmeans (ClusterIndex.train) or from the reference's saved
+    files (ClusterIndex.load); labels of any integer dtype."""
+
+    def __init__(self, vectors, centroids, labels, ctx: Context | None = None):
+        self.ctx = ctx or default_context()
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        cen = np.ascontiguousarray(centroids, dtype=np.float32)
+        lab = np.asarray(labels).ravel()
+        if lab.dtype.kind not in "iu":
+            raise TypeError(f"labels must be integers, got {lab.dtype}")
+        if cen.ndim != 2 or cen.shape[1] != v.shape[1]:
+            raise ValueError("The centroids have the wrong shape")
+        if lab.shape[0] != v.shape[0]:
+            raise ValueError("The labels have the wrong shape")
+        if lab.size and (int(lab.min()) < 0 or int(lab.max()) >= 2 ** 32):
+            raise ValueError("label out of range")
+        self.centroids, self.labels = cen, np.ascontiguousarray(lab.astype(np.uint32))
+        self.n, self.dim, self.nc = v.shape[0], v.shape[1], cen.shape[0]
+        h = vp()
+        _check(lib().pm_cluster_create(self.ctx.h, _p(v, f32p), self.n, self.dim, _p(cen, f32p), self.nc,
+                                       _p(self.labels, u32p), C.byref(h)))
+        self.h = h
+        self.offsets = np.zeros(self.nc + 1, dtype=np.uint64)
+        self.order = np.zeros(self.n, dtype=np.uint32)
+        _check(lib().pm_cluster_info(self.h, None, None, None, _p(self.offsets, u64p), _p(self.order, u32p)))
+
+    @classmethod
+    def train(cls, vectors, nc: int | None = None, niter: int = 20, seed: int = 1, ctx: Context | None = None):
+        """pm.kmeans then the index; nc defaults to int(sqrt(n)) (cluster-search.py:114)."""
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        nc = int(np.sqrt(v.shape[0])) if nc is None else nc
+        cen, labels, _, _ = kmeans(v, nc, niter, seed, ctx=ctx)
+        return cls(v, cen, labels, ctx)
+
+    def save(self, prefix: str) -> None:
+        """The reference's two data files: <prefix>-centroids.npy and <prefix>-labels.npy."""
+        np.save(f"{prefix}-centroids.npy", self.centroids)
+        np.save(f"{prefix}-labels.npy", self.labels)
+
+    @classmethod
+    def load(cls, prefix: str, vectors, ctx: Context | None = None):
+        return cls(vectors, np.load(f"{prefix}-centroids.npy"), np.load(f"{prefix}-labels.npy"), ctx)
+
+    def search(self, queries, k: int, nprobe: int = 1, with_dist: bool = False, with_probed: bool = False):
+        """ids [nq, k] int64 (-1 padded): the k smallest (L2Dist, id) over the rows
+        of each query's nprobe nearest clusters.  with_dist: also dists [nq, k]
+        (+inf padded); with_probed: also probed [nq, nprobe] uint32 and scanned
+        [nq] uint64 (rows scored)."""
+        if not self.h:
+            raise RuntimeError("ClusterIndex is closed")
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        ids = np.zeros((nq, max(k, 0)), dtype=np.int64)
+        d = np.zeros((nq, max(k, 0)), dtype=np.float32)
+        pr = np.zeros((nq, max(nprobe, 0)), dtype=np.uint32)
+        sc = np.zeros(nq, dtype=np.uint64)
+        _check(lib().pm_cluster_search(self.h, _p(q, f32p), nq, k, nprobe, _p(ids, i64p), _p(d, f32p), _p(pr, u32p),
+                                       _p(sc, u64p)))
+        res = (ids,) + ((d,) if with_dist else ()) + ((pr, sc) if with_probed else ())
+        return res if len(res) > 1 else ids
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().pm_cluster_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 GraphANNFrontend = PIRGraphInfo

@@ -27,26 +27,25 @@ template <class F> static void par_for(uint64_t n, F&& f) {
   for (auto& t : th) t.join();
 }
 
-struct KnnDev {   // device copies for the prefilter + re-rank
-  DevBuf x, xb, xl, xn, mx;   // f32 rows, bf16 rows (exact: hi), exact: lo, norms, exact: the largest norm's bits
-  uint32_t dp = 0;
-};
+// KnnDev (pm_host.h): device copies for the prefilter + re-rank.
 // The "_wide" entry points: rows up to 1,024 wide.  Up to kWideFrom they take the
 // narrow path unchanged; above it the kernels of pm_graph_wide.hip.
-static const char* const kWideDimText = "dim must be in [1, 1024]";
+const char* const kWideDimText = "dim must be in [1, 1024]";
 // The "_k128" entry points: the wide ones with 128 prefilter keys per query row.
 static const char* const kK128KText = "k must be in [1, 128]";
 constexpr uint32_t kWideFrom = 192;
-static bool wide_dim_ok(uint64_t dim) { return pmk::knn_pad_dim_wide((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)) != 0; }
+bool wide_dim_ok(uint64_t dim) { return pmk::knn_pad_dim_wide((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)) != 0; }
 // exact: the split rows of pm_knn_exact (hi + lo, norms of the f32 values);
-// wide (exact only): rows above kWideFrom are padded by knn_pad_dim_wide
-static int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDev& d, bool exact, bool wide = false) {
+// wide (exact only): rows above kWideFrom are padded by knn_pad_dim_wide;
+// kind: where v lies (pm_kmeans' centroids are already on the device)
+int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDev& d, bool exact, bool wide,
+               hipMemcpyKind kind) {
   d.dp = wide && dim > kWideFrom ? pmk::knn_pad_dim_wide(dim) : pmk::knn_pad_dim(dim);
   if (!d.dp) return fail(PM_EINVAL, "kNN supports dim <= 192");
   CHK(d.x.reserve(std::max<uint64_t>(4, n * dim * 4)));
   CHK(d.xb.reserve(std::max<uint64_t>(4, n * d.dp * 2)));
   CHK(d.xn.reserve(std::max<uint64_t>(4, n * 4)));
-  HIPCHK(hipMemcpyAsync(d.x.p, v, n * dim * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d.x.p, v, n * dim * 4, kind, c->stream));
   if (!exact) {
     c->timed("to_bf16", (double)n * dim * 4, [&] { pmk::to_bf16(c->stream, d.x.as<float>(), n, dim, d.dp, d.xb.p, d.xn.as<float>()); });
     return 0;
@@ -72,14 +71,9 @@ static int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDe
 // top: the keys kept per query row, knn_top() or, for the _k128 entry points
 // (exact only), knn_top_k128(): the kernels of pm_graph_k128.hip, cand and pref
 // [nq][128], no row judged for n <= 128.
-struct KnnOut {
-  DevBuf cand, out, dist, len, tau, list, nlist, pref, eps;
-  bool stages = false;
-  uint64_t nl = 0;
-};
-static int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, uint64_t nq, uint32_t dim, uint32_t K,
-                      bool self_base, bool want_dist, bool exact, KnnOut& o, uint64_t* fallback,
-                      uint32_t top = pmk::knn_top()) {
+// KnnOut is in pm_host.h.
+int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, uint64_t nq, uint32_t dim, uint32_t K,
+               bool self_base, bool want_dist, bool exact, KnnOut& o, uint64_t* fallback, uint32_t top) {
   hipStream_t st = c->stream;
   const bool k128 = top == pmk::knn_top_k128();
   CHK(o.cand.reserve(std::max<uint64_t>(4, nq * top * 4)));

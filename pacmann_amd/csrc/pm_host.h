@@ -246,6 +246,28 @@ struct pm_ctx {
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
+// ---------------------------------------------------------------------------
+// pm_build.cpp: the exact kNN device path, shared with pm_cluster.cpp
+// (pm_kmeans' assignment and pm_cluster_search's probe are kNN calls with the
+// centroids as base).
+// ---------------------------------------------------------------------------
+struct KnnDev {   // device copies for the prefilter + re-rank
+  DevBuf x, xb, xl, xn, mx;   // f32 rows, bf16 rows (exact: hi), exact: lo, norms, exact: the largest norm's bits
+  uint32_t dp = 0;
+};
+struct KnnOut {   // knn_device's buffers (see there)
+  DevBuf cand, out, dist, len, tau, list, nlist, pref, eps;
+  bool stages = false;
+  uint64_t nl = 0;
+};
+extern const char* const kWideDimText;   // "dim must be in [1, 1024]"
+bool wide_dim_ok(uint64_t dim);
+int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDev& d, bool exact, bool wide = false,
+               hipMemcpyKind kind = hipMemcpyHostToDevice);
+int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, uint64_t nq, uint32_t dim, uint32_t K,
+               bool self_base, bool want_dist, bool exact, KnnOut& o, uint64_t* fallback,
+               uint32_t top = pmk::knn_top());
+
 using Clock = std::chrono::steady_clock;
 static inline double ms_since(Clock::time_point t) {
   return std::chrono::duration<double, std::milli>(Clock::now() - t).count();

@@ -614,4 +614,29 @@ void u8_bias(hipStream_t st, const uint8_t* rows, uint64_t n, uint32_t dim, uint
 void u8_to_f32(hipStream_t st, const uint8_t* rows, uint64_t count, float* out);
 void knn_i8(hipStream_t st, const void* X, const int32_t* xc, uint64_t N, const void* Q, const int32_t* qc, uint64_t M,
             uint32_t dp, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
+// k-means and the cluster search (pm_cluster.hip; pm_kmeans, pm_cluster_*).
+// cluster_sort: order [n] = the ids sorted by (label, id) and offs [nc + 1] = the first position of every
+// label, through keys (label << idbits | id) sorted into keys_out (both [n]); temp of cluster_sort_temp(n, nc)
+// bytes.  kmeans_update: centroid c = the f64 mean of rows order[offs[c] .. offs[c + 1]) in the order of
+// DESIGN.md §10.5, unchanged for an empty cluster.  kmeans_moved: *count += the rows with cur != prev.
+// cluster_gather: out row r = rows[order[r]].  cluster_scan: list e [K] = the K smallest (L2Dist(row r,
+// query work[e].q) bits << 32 | order[r]) keys over the rows [r0, r1) of S, ascending, kNoKey padded;
+// cluster_merge: query q's result = the K smallest keys of lists woff[q] .. woff[q + 1), out / dist [nq][K]
+// and len [nq] as knn_rerank's.
+struct ScanWork {
+  uint64_t r0, r1;   // rows of the cluster-ordered copy, r0 < r1
+  uint32_t q, pad;   // the query row
+};
+constexpr uint32_t kKmeansPartials = 16;   // partial sums per coordinate (part of pm_kmeans' contract)
+size_t cluster_sort_temp(uint64_t n, uint64_t nc);
+hipError_t cluster_sort(hipStream_t st, void* temp, size_t temp_bytes, const uint32_t* labels, uint64_t n, uint64_t nc,
+                        uint64_t* keys, uint64_t* keys_out, uint32_t* order, uint64_t* offs);
+void kmeans_update(hipStream_t st, const float* rows, uint32_t dim, const uint32_t* order, const uint64_t* offs,
+                   uint64_t nc, float* centroids);
+void kmeans_moved(hipStream_t st, const uint32_t* cur, const uint32_t* prev, uint64_t n, uint64_t* count);
+void cluster_gather(hipStream_t st, const float* rows, uint64_t n, uint32_t dim, const uint32_t* order, float* out);
+void cluster_scan(hipStream_t st, const float* S, const uint32_t* order, uint32_t dim, const float* Q,
+                  const ScanWork* work, uint64_t nwork, uint32_t K, uint64_t* lists);
+void cluster_merge(hipStream_t st, const uint64_t* lists, const uint64_t* woff, uint64_t nq, uint32_t K, uint32_t* out,
+                   float* dist, uint32_t* len);
 }  // namespace pmk
