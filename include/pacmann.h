@@ -641,7 +641,7 @@ int pm_robust_prune(pm_ctx* ctx, const float* vectors, uint64_t n, uint64_t dim,
  * dim in [193, 1024] the rows are padded to the next multiple of 64 (dp) and
  * the prefilter walks them in chunks of 64 (k_knn_bf16x3_w, timing name
  * "knn_prefilter_w"); the fallback and robustPrune keep one row in LDS
- * (k_knn_brute_w, k_prune_w).  Only the exact (certified) form exists for wide
+ * (k_knn_brute<64, 1024>, k_prune<false>).  Only the exact (certified) form exists for wide
  * rows: pm_knn's promise for integer rows needs dim * 255^2 < 2^24, i.e. dim
  * <= 258.  The certificate's eps is c_dp (|q|^2 + max |x|^2) + 2^-50 with c_dp =
  * 2 (3 dp + 8) 2^-23 + 2^-16 (1 + 2^-6) + 2^-17: 2.08e-4 at dp 256, 3.91e-4 at

@@ -16,9 +16,8 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libpacmann.so"
-SOURCES = [CSRC / "pm_kernels.hip", CSRC / "pm_query.hip", CSRC / "pm_graph.hip", CSRC / "pm_graph_wide.hip",
-           CSRC / "pm_graph_k128.hip", CSRC / "pm_graph_u8.hip", CSRC / "pm_cluster.hip",
-           CSRC / "pm_shard.hip",
+SOURCES = [CSRC / "pm_kernels.hip", CSRC / "pm_query.hip", CSRC / "pm_graph.hip", CSRC / "pm_graph_u8.hip",
+           CSRC / "pm_cluster.hip", CSRC / "pm_shard.hip",
            CSRC / "pm_drl.hip", CSRC / "pm_knnb.hip", CSRC / "pm_ctx.cpp", CSRC / "pm_engine.cpp",
            CSRC / "pm_search.cpp", CSRC / "pm_group.cpp", CSRC / "pm_devloop.cpp",
            CSRC / "pm_rccl.cpp", CSRC / "pm_build.cpp", CSRC / "pm_cluster.cpp"]

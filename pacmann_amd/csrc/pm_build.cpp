@@ -28,19 +28,18 @@ template <class F> static void par_for(uint64_t n, F&& f) {
 }
 
 // KnnDev (pm_host.h): device copies for the prefilter + re-rank.
-// The "_wide" entry points: rows up to 1,024 wide.  Up to kWideFrom they take the
-// narrow path unchanged; above it the kernels of pm_graph_wide.hip.
+// The "_wide" entry points: rows up to 1,024 wide.  Rows that are not pmk::knn_wide
+// take the narrow path unchanged; the others the chunked kernels.
 const char* const kWideDimText = "dim must be in [1, 1024]";
 // The "_k128" entry points: the wide ones with 128 prefilter keys per query row.
 static const char* const kK128KText = "k must be in [1, 128]";
-constexpr uint32_t kWideFrom = 192;
 bool wide_dim_ok(uint64_t dim) { return pmk::knn_pad_dim_wide((uint32_t)std::min<uint64_t>(dim, UINT32_MAX)) != 0; }
 // exact: the split rows of pm_knn_exact (hi + lo, norms of the f32 values);
-// wide (exact only): rows above kWideFrom are padded by knn_pad_dim_wide;
+// wide (exact only): rows above knn_pad_dim's widths are padded by knn_pad_dim_wide;
 // kind: where v lies (pm_kmeans' centroids are already on the device)
 int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDev& d, bool exact, bool wide,
                hipMemcpyKind kind) {
-  d.dp = wide && dim > kWideFrom ? pmk::knn_pad_dim_wide(dim) : pmk::knn_pad_dim(dim);
+  d.dp = wide && pmk::knn_wide(dim) ? pmk::knn_pad_dim_wide(dim) : pmk::knn_pad_dim(dim);
   if (!d.dp) return fail(PM_EINVAL, "kNN supports dim <= 192");
   CHK(d.x.reserve(std::max<uint64_t>(4, n * dim * 4)));
   CHK(d.xb.reserve(std::max<uint64_t>(4, n * d.dp * 2)));
@@ -69,8 +68,9 @@ int knn_upload(pm_ctx* c, const float* v, uint64_t n, uint32_t dim, KnnDev& d, b
 // (NaN bits where no row was judged: n <= 64); tau and the uncertified list
 // (nl rows, unordered) stay in the struct either way.
 // top: the keys kept per query row, knn_top() or, for the _k128 entry points
-// (exact only), knn_top_k128(): the kernels of pm_graph_k128.hip, cand and pref
-// [nq][128], no row judged for n <= 128.
+// (exact only), knn_top_k128(): cand and pref [nq][128], no row judged for
+// n <= 128.  pmk picks every stage's kernel from (B.dp or dim, top); the host
+// only names the prefilter's timing entry after the same two.
 // KnnOut is in pm_host.h.
 int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, uint64_t nq, uint32_t dim, uint32_t K,
                bool self_base, bool want_dist, bool exact, KnnOut& o, uint64_t* fallback, uint32_t top) {
@@ -100,31 +100,22 @@ int knn_device(pm_ctx* c, const KnnDev& B, uint64_t n, const KnnDev& Q, uint64_t
     CHK(o.eps.reserve(std::max<uint64_t>(4, nq * 4)));
     HIPCHK(hipMemsetAsync(o.eps.p, 0xff, std::max<uint64_t>(4, nq * 4), st));
   }
-  const bool wide = B.dp > kWideFrom;   // rows padded by knn_pad_dim_wide: the kernels of pm_graph_wide.hip
-  if (k128)
-    c->timed(wide ? "knn_prefilter_k128_w" : "knn_prefilter_k128", 2 * pre_bytes, [&] {
-      pmk::knn_prefilter_k128(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
-                              o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
-  else if (wide)
-    c->timed("knn_prefilter_w", 2 * pre_bytes, [&] {
-      pmk::knn_prefilter_x3_w(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
-                              o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
-  else
-    c->timed("knn_prefilter_x3", 2 * pre_bytes, [&] {
-      pmk::knn_prefilter_x3(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp,
-                            o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
+  const bool wide = pmk::knn_wide(B.dp);
+  c->timed(k128 ? (wide ? "knn_prefilter_k128_w" : "knn_prefilter_k128") : (wide ? "knn_prefilter_w" : "knn_prefilter_x3"),
+           2 * pre_bytes, [&] {
+    pmk::knn_prefilter_x3(st, B.xb.p, B.xl.p, B.xn.as<float>(), n, Q.xb.p, Q.xl.p, Q.xn.as<float>(), nq, B.dp, top,
+                          o.cand.as<uint32_t>(), o.tau.as<float>(), pref); });
   c->timed("knn_rerank", rr_bytes, [&] {
-    (k128 ? pmk::knn_rerank_cert_k128 : pmk::knn_rerank_cert)(st, B.x.as<float>(), n, dim, Q.x.as<float>(), nq, o.cand.as<uint32_t>(), K, self_base,
+    pmk::knn_rerank_cert(st, B.x.as<float>(), n, dim, Q.x.as<float>(), nq, o.cand.as<uint32_t>(), K, self_base,
                          o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>(), Q.xn.as<float>(),
-                         o.tau.as<float>(), B.mx.as<uint32_t>(), B.dp, o.list.as<uint64_t>(), o.nlist.as<uint64_t>(),
-                         o.stages ? o.eps.as<float>() : nullptr); });
+                         o.tau.as<float>(), B.mx.as<uint32_t>(), B.dp, top, o.list.as<uint64_t>(),
+                         o.nlist.as<uint64_t>(), o.stages ? o.eps.as<float>() : nullptr); });
   uint64_t nl = 0;
   HIPCHK(hipMemcpyAsync(&nl, o.nlist.p, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   c->timed("knn_brute", (double)nl * n * dim * 4, [&] {
-    (k128 ? pmk::knn_brute_k128 : wide ? pmk::knn_brute_w : pmk::knn_brute)(st, B.x.as<float>(), n, dim, Q.x.as<float>(), o.list.as<uint64_t>(), nl,
-                                               K, self_base, o.out.as<uint32_t>(), o.dist.as<float>(),
-                                               o.len.as<uint32_t>()); });
+    pmk::knn_brute(st, B.x.as<float>(), n, dim, top, Q.x.as<float>(), o.list.as<uint64_t>(), nl, K, self_base,
+                   o.out.as<uint32_t>(), o.dist.as<float>(), o.len.as<uint32_t>()); });
   HIPCHK(hipStreamSynchronize(st));
   o.nl = nl;
   if (fallback) *fallback = nl;
@@ -257,8 +248,6 @@ static int prune_lists(pm_ctx* c, const float* X, uint64_t n, uint32_t dim, cons
                        const std::vector<uint32_t>& huge, const std::vector<uint64_t>& coff,
                        const std::vector<uint32_t>& clen, const std::vector<uint32_t>& conn, uint32_t m, float alpha,
                        std::vector<uint32_t>& P, std::vector<uint32_t>& PL, uint32_t* e, bool wide = false) {
-  // wide: rows above kWideFrom go to k_prune_w (the same lists, results and error flag)
-  const auto prune = wide && dim > kWideFrom ? pmk::prune_w : pmk::prune;
   *e = 0;
   if (big.empty() && huge.empty()) return 0;
   hipStream_t st = c->stream;
@@ -277,9 +266,9 @@ static int prune_lists(pm_ctx* c, const float* X, uint64_t n, uint32_t dim, cons
   HIPCHK(hipMemcpyAsync(dlen.p, clen.data(), n * 4, hipMemcpyHostToDevice, st));
   if (!conn.empty()) HIPCHK(hipMemcpyAsync(dids.p, conn.data(), conn.size() * 4, hipMemcpyHostToDevice, st));
   c->timed("prune", 0.0, [&] {
-    prune(st, X, dim, dv.as<uint32_t>(), big.size(), doff.as<uint64_t>(), 0, dlen.as<uint32_t>(),
-          dids.as<uint32_t>(), m, alpha, dout.as<uint32_t>(), dol.as<uint32_t>(), err.as<uint32_t>(), nullptr,
-          nullptr); });
+    pmk::prune(st, X, dim, wide, dv.as<uint32_t>(), big.size(), doff.as<uint64_t>(), 0, dlen.as<uint32_t>(),
+               dids.as<uint32_t>(), m, alpha, dout.as<uint32_t>(), dol.as<uint32_t>(), err.as<uint32_t>(), nullptr,
+               nullptr); });
   if (!huge.empty()) {
     CHK(dd.reserve(std::max<uint64_t>(4, conn.size() * 4)));
     CHK(dpos.reserve(std::max<uint64_t>(4, conn.size() * 4)));
@@ -307,9 +296,9 @@ static int prune_lists(pm_ctx* c, const float* X, uint64_t n, uint32_t dim, cons
     });
     if (!pos.empty()) HIPCHK(hipMemcpyAsync(dpos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, st));
     c->timed("prune", 0.0, [&] {
-      prune(st, X, dim, dh.as<uint32_t>(), huge.size(), doff.as<uint64_t>(), 0, dlen.as<uint32_t>(),
-            dids.as<uint32_t>(), m, alpha, dout.as<uint32_t>(), dol.as<uint32_t>(), err.as<uint32_t>(),
-            dpos.as<uint32_t>(), dd.as<float>()); });
+      pmk::prune(st, X, dim, wide, dh.as<uint32_t>(), huge.size(), doff.as<uint64_t>(), 0, dlen.as<uint32_t>(),
+                 dids.as<uint32_t>(), m, alpha, dout.as<uint32_t>(), dol.as<uint32_t>(), err.as<uint32_t>(),
+                 dpos.as<uint32_t>(), dd.as<float>()); });
   }
   P.resize(n * m);
   PL.resize(n);
@@ -352,9 +341,8 @@ static int build_graph_core(pm_ctx* c, uint64_t n, uint64_t dim, uint64_t m, flo
   auto t1 = Clock::now();
   // first pass: robustPrune(vectors, u, candidates, m, alpha) (:413-414)
   c->timed("prune", 0.0, [&] {
-    (wide && dim > kWideFrom ? pmk::prune_w : pmk::prune)(
-        st, bc.x, (uint32_t)dim, nullptr, n, nullptr, K, bc.len, bc.out,
-        (uint32_t)m, alpha, g1.as<uint32_t>(), len1.as<uint32_t>(), err.as<uint32_t>(), nullptr, nullptr); });
+    pmk::prune(st, bc.x, (uint32_t)dim, wide, nullptr, n, nullptr, K, bc.len, bc.out, (uint32_t)m, alpha,
+               g1.as<uint32_t>(), len1.as<uint32_t>(), err.as<uint32_t>(), nullptr, nullptr); });
   std::vector<uint32_t> G(n * m), L1(n);
   uint32_t e = 0;
   HIPCHK(hipMemcpyAsync(G.data(), g1.p, n * m * 4, hipMemcpyDeviceToHost, st));
@@ -597,8 +585,8 @@ extern "C" int pm_build_graph_u8(pm_ctx* c, const uint8_t* vectors, uint64_t n, 
       });
 }
 
-// pm_robust_prune and pm_robust_prune_wide: k_prune (wide, rows above kWideFrom:
-// k_prune_w) on given lists, through the build's own second pass (prune_lists);
+// pm_robust_prune and pm_robust_prune_wide: k_prune (wide, rows above
+// knn_pad_dim's: its form with one row in LDS) on given lists, through the build's own second pass (prune_lists);
 // every list by the LDS sort, or every list presorted.
 static int robust_prune_impl(pm_ctx* c, const float* vectors, uint64_t n, uint64_t dim, const uint32_t* verts,
                              uint64_t nverts, const uint64_t* offs, const uint32_t* lens, const uint32_t* ids,

@@ -7,8 +7,8 @@
 //   k_kmeans_update     the centroid update in a fixed f64 summation order
 //   k_kmeans_moved      how many rows changed label (an integer count)
 //   k_cluster_gather    the rows in cluster order
-//   k_cluster_scan      k_knn128_brute over a row range of the cluster-ordered
-//                       copy, keys carrying the original id
+//   k_cluster_scan      the brute-force stream of pm_graph_dev.h over a row range of
+//                       the cluster-ordered copy, keys carrying the original id
 //   k_cluster_merge     a query's lists merged into its first K
 //
 // The distances of every assignment and probe come from the exact kNN kernels
@@ -131,57 +131,31 @@ __global__ void __launch_bounds__(kBlock) k_cluster_gather(const float* __restri
   }
 }
 
-// k_knn128_brute (pm_graph_k128.hip) over the rows [r0, r1) of the
-// cluster-ordered copy S instead of over all N, the key carrying order[r]: one
-// workgroup per work item (a query and a probed cluster, or a piece of a large
-// one), the query row in LDS, the waves striding the rows eight at a time with
-// a sorted top-128 each, merged by wave 0, which writes the first K keys.
-struct ScanLds {
-  uint64_t top[kBlock / 64][kKnnTop2];
-  float q[kScanMaxDim];
-};
-
+// knn_brute_stream (pm_graph_dev.h) over the rows [r0, r1) of the
+// cluster-ordered copy S, the key carrying order[r]: one workgroup per work
+// item (a query and a probed cluster, or a piece of a large one); wave 0 writes
+// the first K keys of the merged top-128.
 __global__ void __launch_bounds__(kBlock) k_cluster_scan(const float* __restrict__ S,
                                                          const uint32_t* __restrict__ order, uint32_t dim,
                                                          const float* __restrict__ Q,
                                                          const pmk::ScanWork* __restrict__ work, uint64_t nwork,
                                                          uint32_t K, uint64_t* __restrict__ lists) {
-  __shared__ ScanLds L;
-  constexpr uint32_t W = kBlock / 64;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 3, k = lane & 7;
+  __shared__ BruteLds<kKnnTop2, kScanMaxDim> L;
+  const uint32_t lane = threadIdx.x & 63;
   for (uint64_t e = blockIdx.x; e < nwork; e += gridDim.x) {
     const pmk::ScanWork wk = work[e];
-    for (uint32_t i = tid; i < dim; i += kBlock) L.q[i] = Q[(uint64_t)wk.q * dim + i];
-    __syncthreads();
-    Key2 t = {kNoKey, kNoKey};
-    for (uint64_t r0 = wk.r0 + 8 * w; r0 < wk.r1; r0 += 8 * W) {   // uniform per wave: every lane stays active
-      const uint64_t r = r0 + g;
-      const bool ok = r < wk.r1;
-      const uint64_t rr = ok ? r : wk.r0;
-      const float d = l2_group8(S + rr * dim, L.q, dim, k);
-      const uint64_t key = ok ? (((uint64_t)__float_as_uint(d) << 32) | order[rr]) : kNoKey;
-      uint64_t m = __ballot(k == 0 && key < readlane64(t.b, 63));
-      while (m) {
-        const int src = __builtin_ctzll(m);
-        m &= m - 1;
-        t = knn_insert128(t, readlane64(key, src), lane);
-      }
+    const TopKeys<kKnnTop2> t = knn_brute_stream(L, S, dim, Q + (uint64_t)wk.q * dim, wk.r0, wk.r1, order);
+    if (threadIdx.x < 64) {
+      #pragma unroll
+      for (int i = 0; i < t.H; ++i)
+        if (64 * i + lane < K) lists[e * K + 64 * i + lane] = t.v[i];
     }
-    L.top[w][lane] = t.a;
-    L.top[w][64 + lane] = t.b;
-    __syncthreads();
-    if (w == 0) {
-      for (uint32_t o = 1; o < W; ++o)
-        for (uint32_t i = 0; i < kKnnTop2; ++i) t = knn_insert128(t, L.top[o][i], lane);
-      if (lane < K) lists[e * K + lane] = t.a;
-      if (64 + lane < K) lists[e * K + 64 + lane] = t.b;
-    }
-    __syncthreads();   // L.q and L.top are reused by the next work item
+    __syncthreads();   // L is reused by the next work item
   }
 }
 
 // One wave per query: the K smallest keys of its lists (each ascending, kNoKey
-// padded), written as knn_emit128 writes a row.
+// padded), written as TopKeys::emit writes a row.
 __global__ void __launch_bounds__(kBlock) k_cluster_merge(const uint64_t* __restrict__ lists,
                                                           const uint64_t* __restrict__ woff, uint64_t nq, uint32_t K,
                                                           uint32_t* __restrict__ out, float* __restrict__ dist_out,
@@ -189,14 +163,14 @@ __global__ void __launch_bounds__(kBlock) k_cluster_merge(const uint64_t* __rest
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint64_t q = (uint64_t)blockIdx.x * (kBlock / 64) + w;
   if (q >= nq) return;
-  Key2 t = {kNoKey, kNoKey};
+  TopKeys<kKnnTop2> t = TopKeys<kKnnTop2>::empty();
   for (uint64_t e = woff[q]; e < woff[q + 1]; ++e)
     for (uint32_t i = 0; i < K; ++i) {
       const uint64_t key = lists[e * K + i];   // the same address in every lane
       if (key == kNoKey) break;
-      t = knn_insert128(t, key, lane);
+      t.insert(key, lane);
     }
-  knn_emit128(t, q, K, 0, lane, out, dist_out, len);
+  t.emit(q, K, 0, lane, out, dist_out, len);
 }
 
 }  // namespace pm

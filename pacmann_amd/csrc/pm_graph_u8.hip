@@ -12,9 +12,8 @@
 //                 mfma_i32_32x32x32_i8, and the first K of them written out
 //   k_u8_to_f32   the rows as f32, for the build's robustPrune stages
 //
-// The tile walk, the insert / merge phase and the 128-key list are
-// k_knn128_bf16x3's (pm_graph_k128.hip); the list helpers are pm_graph_dev.h's,
-// used as they are.
+// The tile walk is k_knn_bf16x3<DP, 128>'s (pm_graph.hip) with one operand tile;
+// the lists, the tile epilogue and the emit are pm_graph_dev.h's.
 #include <hip/hip_runtime.h>
 
 #include "pm_internal.h"
@@ -66,11 +65,7 @@ __global__ void __launch_bounds__(kBlock) k_u8_to_f32(const uint8_t* __restrict_
 }
 
 template <int DP>
-struct KnnU8Lds {
-  uint64_t top[kKnnRows][kKnnTop2];         // sorted ascending per row
-  uint64_t buf[kKnnRows][kU8Cols];          // this tile's keys below the row threshold
-  uint32_t cnt[kKnnRows];
-  uint32_t any[2];
+struct KnnU8Lds : KnnLists<kKnnTop2, kU8Cols> {
   int8_t b[kU8Cols][DP + kU8Pad];           // padded rows: conflict-free 16-B fragment reads
 };
 static_assert(sizeof(KnnU8Lds<64>) == 103688 && sizeof(KnnU8Lds<256>) == 115976, "LDS budget of DESIGN.md §10.4");
@@ -104,10 +99,7 @@ __global__ void __launch_bounds__(kU8Threads) k_knn_i8(const int8_t* __restrict_
   const uint32_t rb = 32 * (w & 1), cb = 32 * (w >> 1);
   const uint32_t r32 = lane & 31, h = lane >> 5;
   const uint64_t row0 = (uint64_t)blockIdx.x * kKnnRows;
-
-  for (uint32_t i = tid; i < kKnnRows * kKnnTop2; i += kU8Threads) (&L.top[0][0])[i] = kNoKey;
-  if (tid < kKnnRows) L.cnt[tid] = 0;
-  if (tid < 2) L.any[tid] = 0;
+  knn_lists_init<kU8Threads>(L, tid);
 
   i32x4 a[KS];
   {
@@ -120,12 +112,7 @@ __global__ void __launch_bounds__(kU8Threads) k_knn_i8(const int8_t* __restrict_
   }
   int32_t qcr[16];
   uint32_t thi[16];
-  #pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const uint64_t qr = row0 + rb + (i & 3) + 8 * (i >> 2) + 4 * h;
-    qcr[i] = qr < M ? qc[qr] : 0;
-    thi[i] = 0xffffffffu;
-  }
+  knn_rows_init(qc, row0, M, rb, h, qcr, thi);
   const uint64_t T = (N + kU8Cols - 1) / kU8Cols;
   uint4 pre[PER];
   auto load_tile = [&](uint64_t t) {
@@ -148,6 +135,7 @@ __global__ void __launch_bounds__(kU8Threads) k_knn_i8(const int8_t* __restrict_
   load_tile(0);
   store_tile();
   __syncthreads();
+  uint32_t par = 0;   // t & 1, carried by knn_tile_end
   for (uint64_t t = 0; t < T; ++t) {
     if (t + 1 < T) load_tile(t + 1);   // in flight during the MFMAs
     i32x16 acc = {};
@@ -157,49 +145,17 @@ __global__ void __launch_bounds__(kU8Threads) k_knn_i8(const int8_t* __restrict_
       acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[s], b, acc, 0, 0, 0);
     }
     const uint64_t col = t * kU8Cols + cb + r32;
-    if (col < N) {
-      const int32_t cn = xc[col];
-      #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const uint32_t lr = rb + (i & 3) + 8 * (i >> 2) + 4 * h;
-        const uint32_t db = (uint32_t)(qcr[i] + cn - 2 * acc[i]);
-        if (db <= thi[i]) {
-          const uint64_t key = ((uint64_t)db << 32) | (uint32_t)col;
-          if (db < thi[i] || key < L.top[lr][kKnnTop2 - 1]) {
-            const uint32_t slot = atomicAdd(&L.cnt[lr], 1u);
-            L.buf[lr][slot] = key;
-            L.any[t & 1] = 1;
-          }
-        }
-      }
-    }
-    if (tid == 0) L.any[(t + 1) & 1] = 0;
-    __syncthreads();
-    const bool merged = L.any[t & 1] != 0;   // uniform
-    if (merged) {
-      for (uint32_t r = w * MR; r < w * MR + MR; ++r) {
-        const uint32_t n = L.cnt[r];
-        if (n) knn_merge_row128(L.top[r], L.buf[r], n, lane);
-      }
-    }
-    if (t + 1 < T) store_tile();
-    __syncthreads();
-    if (merged) {
-      if (lane < MR) L.cnt[w * MR + lane] = 0;
-      #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const uint32_t lr = rb + (i & 3) + 8 * (i >> 2) + 4 * h;
-        thi[i] = (uint32_t)(L.top[lr][kKnnTop2 - 1] >> 32);
-      }
-    }
-    // cnt resets must land before the next tile's inserts
-    if (merged) __syncthreads();
+    knn_tile_end<kU8Threads>(
+        L, par, col, N, xc, rb, h, thi, [=](int i, int32_t cn) { return (uint32_t)(qcr[i] + cn - 2 * acc[i]); },
+        [&] { if (t + 1 < T) store_tile(); });
   }
   for (uint32_t r = w * MR; r < w * MR + MR; ++r) {
     const uint64_t qr = row0 + r;
     if (qr < M) {   // uniform per wave
-      const Key2 t = {u8_key_f32(L.top[r][lane]), u8_key_f32(L.top[r][64 + lane])};
-      knn_emit128(t, qr, K, self_base, lane, out, dist_out, len);
+      TopKeys<kKnnTop2> t = TopKeys<kKnnTop2>::load(L.top[r], lane);
+      #pragma unroll
+      for (int i = 0; i < t.H; ++i) t.v[i] = u8_key_f32(t.v[i]);
+      t.emit(qr, K, self_base, lane, out, dist_out, len);
     }
   }
 }
@@ -207,28 +163,23 @@ __global__ void __launch_bounds__(kU8Threads) k_knn_i8(const int8_t* __restrict_
 }  // namespace pm
 
 namespace pmk {
-static inline unsigned gcdiv_u8(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }
-
 uint32_t knn_u8_max_dim() { return kU8MaxDim; }
 uint32_t knn_u8_pad_dim(uint32_t dim) { return dim == 0 || dim > (uint32_t)kU8MaxDim ? 0 : (dim + 63) / 64 * 64; }
 
 void u8_bias(hipStream_t st, const uint8_t* rows, uint64_t n, uint32_t dim, uint32_t dp, void* out, int32_t* cst) {
   if (!n) return;
-  const uint64_t blocks = (n + kBlock / 64 - 1) / (kBlock / 64);
-  hipLaunchKernelGGL(k_u8_bias, dim3((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(kBlock), 0, st, rows,
-                     n, dim, dp, (uint8_t*)out, cst);
+  hipLaunchKernelGGL(k_u8_bias, dim3(gclamp(gcdiv(n, kBlock / 64))), dim3(kBlock), 0, st, rows, n, dim, dp,
+                     (uint8_t*)out, cst);
 }
 void u8_to_f32(hipStream_t st, const uint8_t* rows, uint64_t count, float* out) {
   if (!count) return;
-  const uint64_t blocks = (count + kBlock - 1) / kBlock;
-  hipLaunchKernelGGL(k_u8_to_f32, dim3((unsigned)(blocks < (1u << 20) ? blocks : (1u << 20))), dim3(kBlock), 0, st,
-                     rows, count, out);
+  hipLaunchKernelGGL(k_u8_to_f32, dim3(gclamp((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, rows, count, out);
 }
 // dp: 64, 128, 192 or 256 (knn_u8_pad_dim); K in [1, 128]
 void knn_i8(hipStream_t st, const void* X, const int32_t* xc, uint64_t N, const void* Q, const int32_t* qc, uint64_t M,
             uint32_t dp, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len) {
   if (!M) return;
-  const dim3 grid(gcdiv_u8(M, kKnnRows)), block(kU8Threads);
+  const dim3 grid(gcdiv(M, kKnnRows)), block(kU8Threads);
   const int8_t *x = (const int8_t*)X, *q = (const int8_t*)Q;
   switch (dp) {
     case 64: hipLaunchKernelGGL(k_knn_i8<64>, grid, block, 0, st, x, xc, N, q, qc, M, K, (int)self_base, out, dist, len); break;

@@ -541,9 +541,16 @@ uint32_t knn_batch_kcap(uint64_t parallel, uint64_t max_step, uint64_t m);
 uint64_t knn_batch_lds(uint32_t kcap, uint32_t dim, uint32_t nb, uint32_t ns);
 bool knn_batch_ok(uint64_t dim, uint64_t m, uint64_t ns, uint64_t max_step, uint64_t parallel);
 void knn_batch(hipStream_t st, const KnbArgs& A);
-// graph construction and ground truth (pm_graph.hip)
-uint32_t knn_pad_dim(uint32_t dim);   // bf16 row width for the prefilter (0: unsupported)
-uint32_t knn_top();                   // prefilter candidates per query row
+// graph construction and ground truth (pm_graph.hip).  One entry per stage; each picks its kernel's
+// instantiation from the row width and top, the keys kept per query row (knn_top() or knn_top_k128()).
+inline unsigned gcdiv(uint64_t a, uint64_t b) { return (unsigned)((a + b - 1) / b); }
+// the grid of a kernel that loops over gridDim.x: at most 2^20 blocks
+inline unsigned gclamp(uint64_t blocks) { return (unsigned)(blocks < (1u << 20) ? blocks : (1u << 20)); }
+uint32_t knn_pad_dim(uint32_t dim);        // bf16 row width of rows held whole, 128 or 192 (0: too wide)
+uint32_t knn_pad_dim_wide(uint32_t dim);   // ... of any row: the next multiple of 64 (0: dim 0 or above 1,024)
+bool knn_wide(uint32_t width);             // a dim or padded width above knn_pad_dim's: the chunked / one-row-in-LDS kernels
+uint32_t knn_top();                        // 64
+uint32_t knn_top_k128();                   // 128
 uint32_t prune_max_list();
 uint32_t prune_max_dim();
 uint32_t prune_max_m();
@@ -552,58 +559,33 @@ void knn_prefilter(hipStream_t st, const void* X, const float* xn, uint64_t N, c
                    uint64_t M, uint32_t dp, uint32_t* out, uint32_t* out_hi = nullptr);
 void knn_rerank(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
                 const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
-// the exact variants (pm_knn_exact): split rows hi + lo with f32 norms and the largest norm's bits,
-// the three-product prefilter with each row's 64th prefilter distance tau, the re-rank with the
-// certificate (uncertified rows appended to list, counted in *nlist), the brute-force fallback of
-// the listed rows, and the relative part of the certificate's eps for rows of width dp
+// the exact variants (pm_knn_exact, _wide, _k128): split rows hi + lo with f32 norms and the largest
+// norm's bits; the three-product prefilter at any padded width (128, 192, or a multiple of 64 up to
+// 1,024) with out / out_hi [M][top] and each row's last prefilter distance tau; the re-rank with the
+// certificate (uncertified rows appended to list, counted in *nlist); the brute-force fallback of the
+// listed rows at any dim up to 1,024; and the relative part of the certificate's eps at width dp
 void to_bf16x2(hipStream_t st, const float* rows, uint64_t n, uint32_t dim, uint32_t dp, void* hi, void* lo,
                float* norms, uint32_t* maxnorm);
 void knn_prefilter_x3(hipStream_t st, const void* Xh, const void* Xl, const float* xn, uint64_t N, const void* Qh,
-                      const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau,
-                      uint32_t* out_hi = nullptr);
+                      const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t top, uint32_t* out,
+                      float* tau, uint32_t* out_hi = nullptr);
 float knn_cert_rel(uint32_t dp);
 void knn_rerank_cert(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
                      const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len,
-                     const float* qn, const float* tau, const uint32_t* maxnorm, uint32_t dp, uint64_t* list,
-                     uint64_t* nlist, float* eps_out = nullptr);
-void knn_brute(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, const uint64_t* list,
-               uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
-void prune(hipStream_t st, const float* X, uint32_t dim, const uint32_t* verts, uint64_t nverts,
+                     const float* qn, const float* tau, const uint32_t* maxnorm, uint32_t dp, uint32_t top,
+                     uint64_t* list, uint64_t* nlist, float* eps_out = nullptr);
+void knn_brute(hipStream_t st, const float* X, uint64_t N, uint32_t dim, uint32_t top, const float* Q,
+               const uint64_t* list, uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist,
+               uint32_t* len);
+// wide: the caller is an entry point for rows up to 1,024; its rows above knn_pad_dim's take the form
+// with one row in LDS, every other call the form with the accepted rows in LDS (dim <= prune_max_dim())
+void prune(hipStream_t st, const float* X, uint32_t dim, bool wide, const uint32_t* verts, uint64_t nverts,
            const uint64_t* offs, uint64_t stride, const uint32_t* lens, const uint32_t* ids, uint32_t m,
            float alpha, uint32_t* out, uint32_t* out_len, uint32_t* err, const uint32_t* sorted_pos = nullptr,
            const float* dist_g = nullptr);
 // L2Dist of every candidate of the listed vertices (hub lists above prune_max_list())
 void cand_dist(hipStream_t st, const float* X, uint32_t dim, const uint32_t* verts, uint64_t nverts,
                const uint64_t* offs, const uint32_t* lens, const uint32_t* ids, float* dist_g);
-// rows of 193 to 1,024 dimensions (pm_graph_wide.hip; pm_knn_wide, pm_build_graph_wide): the padded
-// width (the next multiple of 64; 0 for dim 0 or above 1,024), the K-chunked three-product
-// prefilter at that width, and the brute-force and robustPrune kernels with one row in LDS.
-// Arguments as knn_prefilter_x3, knn_brute and prune; to_bf16x2, knn_rerank_cert and cand_dist
-// take any width.
-uint32_t knn_pad_dim_wide(uint32_t dim);
-void knn_prefilter_x3_w(hipStream_t st, const void* Xh, const void* Xl, const float* xn, uint64_t N, const void* Qh,
-                        const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau,
-                        uint32_t* out_hi = nullptr);
-void knn_brute_w(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, const uint64_t* list,
-                 uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
-void prune_w(hipStream_t st, const float* X, uint32_t dim, const uint32_t* verts, uint64_t nverts,
-             const uint64_t* offs, uint64_t stride, const uint32_t* lens, const uint32_t* ids, uint32_t m,
-             float alpha, uint32_t* out, uint32_t* out_len, uint32_t* err, const uint32_t* sorted_pos = nullptr,
-             const float* dist_g = nullptr);
-// 128 prefilter keys per query row (pm_graph_k128.hip; pm_knn_k128, pm_build_graph_k128): out and
-// out_hi are [M][128], tau the 128th prefilter distance, K up to 128.  knn_prefilter_k128 takes
-// every padded width (128, 192, or a multiple of 64 up to 1,024), knn_brute_k128 every dim up to
-// 1,024.  Arguments as knn_prefilter_x3_w, knn_rerank_cert and knn_brute.
-uint32_t knn_top_k128();
-void knn_prefilter_k128(hipStream_t st, const void* Xh, const void* Xl, const float* xn, uint64_t N, const void* Qh,
-                        const void* Ql, const float* qn, uint64_t M, uint32_t dp, uint32_t* out, float* tau,
-                        uint32_t* out_hi = nullptr);
-void knn_rerank_cert_k128(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, uint64_t M,
-                          const uint32_t* cand, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len,
-                          const float* qn, const float* tau, const uint32_t* maxnorm, uint32_t dp, uint64_t* list,
-                          uint64_t* nlist, float* eps_out = nullptr);
-void knn_brute_k128(hipStream_t st, const float* X, uint64_t N, uint32_t dim, const float* Q, const uint64_t* list,
-                    uint64_t nlist, uint32_t K, bool self_base, uint32_t* out, float* dist, uint32_t* len);
 // uint8 rows on the int8 matrix cores (pm_graph_u8.hip; pm_knn_u8, pm_build_graph_u8): u8_bias writes
 // n rows of dp bytes (x ^ 0x80, 0 padded; dp = knn_u8_pad_dim(dim): the next multiple of 64, 0 above
 // knn_u8_max_dim()) and the rows' int32 constants; knn_i8 the first K (K <= 128) of every query

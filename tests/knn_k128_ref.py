@@ -1,4 +1,4 @@
-"""The data of the 128-key exact kNN's tests (pm_graph_k128.hip, DESIGN.md
+"""The data of the 128-key exact kNN's tests (pm_graph.hip, DESIGN.md
 §10.3).  numpy only: no GPU, none of the code under test.  The value families,
 the padding rule and the bound are tests/knn_ref.py's and tests/knn_wide_ref.py's;
 tests/test_abi_k128.py checks, with this module and the oracle alone, the

@@ -1,4 +1,4 @@
-"""The plain reference of the wide exact kNN's stages (pm_graph_wide.hip,
+"""The plain reference of the wide exact kNN's stages (pm_graph.hip,
 DESIGN.md §10.2) and the data of its edge tests.  numpy only: no GPU, none of
 the code under test.  The value families, the bound and the robustPrune data
 are tests/knn_ref.py's; the padding rule and the split / norm order are

@@ -1,6 +1,6 @@
 """pm_build_graph_k128 against the oracle's graph, row for row: m from 43 to 64
 (int(1.5 m) + self above the 64-key list) through the 128-key kNN and the
-unchanged k_prune / k_prune_w, and m = 32 against pm_build_graph_wide."""
+unchanged k_prune / k_prune<false>, and m = 32 against pm_build_graph_wide."""
 import numpy as np
 import pytest
 
@@ -37,7 +37,7 @@ def test_degree_64_more_than_32_accepts(ctx, oracle):
 
 
 def test_degree_48_wide_rows(ctx, oracle):
-    """n = 300, d = 960, m = 48: K = 72, the wide prefilter and k_prune_w."""
+    """n = 300, d = 960, m = 48: K = 72, the wide prefilter and k_prune<false>."""
     v = K.clustered_floats(300, 960, centres=6)
     g, _, runs = build_timed(ctx, v, 48)
     assert np.array_equal(g, oracle.build_graph(v, 48, 1.2, 1))

@@ -1,5 +1,5 @@
 """pm_build_graph_wide against oracle.build_graph row for row: the wide kNN
-candidates (K = int(1.5 m) + self), k_prune_w in both passes and the host's
+candidates (K = int(1.5 m) + self), k_prune<false> in both passes and the host's
 edge work, at rows of 200 to 960 dimensions."""
 import numpy as np
 import pytest

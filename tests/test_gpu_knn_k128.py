@@ -1,5 +1,5 @@
 """pm_knn_k128 end to end against the oracle: 128 prefilter keys per query row
-(k_knn128_bf16x3 for dp 128 / 192, k_knn128_bf16x3_w above), the certificate
+(k_knn_bf16x3<DP, 128> for dp 128 / 192, k_knn_bf16x3_w<128, 32> above), the certificate
 against the 128th prefilter distance and the 128-key brute-force kernels
 (DESIGN.md §10.3), on the tile, pad, chunk and list edges, for k up to 128."""
 import numpy as np

@@ -1,6 +1,6 @@
 """pm_knn_wide end to end against the oracle: rows of 193 to 1,024 dimensions
 through the K-chunked prefilter k_knn_bf16x3_w, the certificate and the wide
-brute-force kernel k_knn_brute_w, on the tile, pad and chunk
+brute-force kernel k_knn_brute<64, 1024>, on the tile, pad and chunk
 edges; and the narrow routing for dim <= 192."""
 import numpy as np
 import pytest
@@ -77,7 +77,7 @@ def test_identical_rows_tie_by_id(ctx, oracle):
 @pytest.mark.parametrize("dim", [320, 1023])
 def test_one_huge_row_uncertifies_all(ctx, oracle, dim):
     """One base row of norm about 2^100 among unit rows: eps follows the largest
-    norm, so every row goes to k_knn_brute_w (dim 320 = 5 x 64, dim 1,023 with a
+    norm, so every row goes to k_knn_brute<64, 1024> (dim 320 = 5 x 64, dim 1,023 with a
     scalar tail of 7); the result is the oracle's."""
     import pacmann_amd as pm
     v, q = W.huge_row_data(dim)

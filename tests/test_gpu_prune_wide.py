@@ -1,4 +1,4 @@
-"""k_prune_w against oracle.robust_prune and knn_ref.prune_trace, through
+"""k_prune<false> against oracle.robust_prune and knn_ref.prune_trace, through
 pm_robust_prune_wide, at rows of 257, 960 and 1,024 dimensions: by the kernel's
 own LDS sort and in the presorted form of hub lists; and the narrow routing."""
 import numpy as np
