@@ -58,7 +58,8 @@ int         pm_ctx_sync(pm_ctx* ctx);
 int         pm_ctx_mem_info(pm_ctx* ctx, uint64_t* free_bytes, uint64_t* total_bytes);
 /* Per-kernel timing.  Level 1: HIP events around the preprocessing and leaf
  * kernels on the stream they run on ("prep_offsets", "prep_fold",
- * "prep_repl", "l2_rows", "ip_scan", "prf", server "answer").  Level 2 also
+ * "prep_repl", "l2_rows", "ip_scan", "prf", server "answer" and
+ * "server_answer").  Level 2 also
  * times the kernels of every online step ("step", "hint_match", "resolve",
  * "gather", "answer") with events carried in their own dispatch packets
  * (hipExtLaunchKernelGGL); steps are not synchronised for it (the events are
@@ -309,6 +310,31 @@ int  pm_batchpir_group_query(pm_batchpir_group* g, const uint64_t* ids, uint64_t
 int  pm_batchpir_group_preprocessing(pm_batchpir_group* g);
 void pm_batchpir_group_destroy(pm_batchpir_group* g);
 int  pm_batchpir_subconfig(pm_batchpir* h, uint64_t partition, pm_pir_config* cfg);
+/* The server role alone, for clients that keep their keys and hints elsewhere
+ * (DESIGN.md §6.6): the batch PIR's partitions are PartitionNum servers
+ * (batch-pir.go:62-85), and row s of out is PianoPIRServer.PrivateQuery
+ * (pir.go:65-88) of the offset set offsets[s*stride .. s*stride + SetSize(P))
+ * over partition P = parts[s]: the XOR over chunks i < SetSize(P) of P's row
+ * i*ChunkSize(P) + offsets[i], a term with i*ChunkSize + offsets[i] >=
+ * DBSize(P) skipped (pir.go:75-77), words [DBEntrySize & ~3, DBEntrySize) zero
+ * (EntryXor).  pm_batchpir_subconfig gives each partition's DBSize, ChunkSize
+ * and SetSize; offsets past SetSize(P) inside the stride are ignored.
+ * The call reads the handle's DB only (a graph server's packed row image where
+ * it has one: "host_server_answer_packed" counts those launches) and neither
+ * reads nor writes keys, hints, counters, cache or id stream, so it may run
+ * between client calls and works on a handle never preprocessed, on a
+ * pm_batchpir_create_client handle and on pm_graph_pir(g).  Synchronous; sets
+ * go up and answers come down in chunks of 65,536, one "server_answer" launch
+ * (timing level 1) each.
+ * PM_EINVAL, before any HIP call and with out untouched: a NULL argument;
+ * "stride must be >= the largest SetSize" (pm_batchpir_max_set_size);
+ * "partition out of range"; "partition not on this shard"; "offset out of
+ * range" for one of a set's first SetSize offsets >= ChunkSize (the reference
+ * would read past the chunk).  nq == 0 returns 0. */
+int  pm_batchpir_server_answer(pm_batchpir* h, const uint32_t* parts /* nq */,
+                               const uint32_t* offsets /* nq x stride */, uint64_t stride,
+                               uint64_t nq, uint64_t* out /* nq x DBEntrySize */);
+uint64_t pm_batchpir_max_set_size(pm_batchpir* h);   /* max SetSize over the handle's partitions; 0 for NULL */
 /* The speculation record of this handle's last step (test hook), where the
  * fused step kernel (k_step, "host_path_step") ran it on a context created with
  * PM_STEP_SPEC=1: *nsub words in sub-query order (partition-major, qn slots per

@@ -124,6 +124,8 @@ SIGNATURES = {
     "pm_batchpir_stats_get": (C.c_int, [vp, C.POINTER(BatchStats)]),
     "pm_batchpir_subconfig": (C.c_int, [vp, u64, C.POINTER(PirConfig)]),
     "pm_batchpir_step_spec": (C.c_int, [vp, C.POINTER(C.c_uint32), u64, C.POINTER(u64)]),
+    "pm_batchpir_server_answer": (C.c_int, [vp, u32p, u32p, u64, u64, u64p]),
+    "pm_batchpir_max_set_size": (u64, [vp]),
     "pm_pir_export": (C.c_int, [vp, u32p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "pm_batchpir_export": (C.c_int, [vp, u64, u32p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "pm_graph_create": (C.c_int, [vp, u64, u64, u64, f32p, u32p, C.c_int, C.c_int, u64, u64, C.POINTER(vp)]),
@@ -617,6 +619,33 @@ class SimpleBatchPianoPIR:
         c = PirConfig()
         _check(lib().pm_batchpir_subconfig(self.h, i, C.byref(c)))
         return c.asdict()
+
+    @property
+    def max_set_size(self) -> int:
+        """The largest SetSize over the partitions (pm_batchpir_max_set_size):
+        the least stride ServerAnswer takes."""
+        return int(lib().pm_batchpir_max_set_size(self.h))
+
+    def ServerAnswer(self, parts, offsets) -> np.ndarray:
+        """The server role alone (pm_batchpir_server_answer): for each set s,
+        PianoPIRServer.PrivateQuery (pir.go:65-88) of offsets[s, :SetSize] over
+        partition parts[s].  parts: [nq]; offsets: [nq, stride] uint32 with
+        stride >= max_set_size (the tail of a row is ignored).  Returns
+        [nq, DBEntrySize] uint64.  Uses the DB only: no client state is read
+        or changed, so no preprocessing is needed."""
+        o = np.asarray(offsets)
+        if o.dtype != np.uint32:
+            raise TypeError("offsets must be uint32")
+        if o.ndim != 2:
+            raise ValueError("offsets must be [nq, stride]")
+        o = np.ascontiguousarray(o)
+        p = np.ascontiguousarray(parts, dtype=np.uint32).ravel()
+        if len(p) != o.shape[0]:
+            raise ValueError("one partition per offset set")
+        out = np.zeros((o.shape[0], self.E), dtype=np.uint64)
+        _check(lib().pm_batchpir_server_answer(self.h, _p(p, u32p), _p(o, u32p), o.shape[1], o.shape[0],
+                                               _p(out, u64p)))
+        return out
 
     def LocalStorageSize(self) -> float:
         return self.stats()["LocalStorage"]

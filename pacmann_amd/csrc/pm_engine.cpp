@@ -1375,6 +1375,72 @@ extern "C" int pm_batchpir_subconfig(pm_batchpir* h, uint64_t p, pm_pir_config* 
   c->PrimaryHintNum = ph.d.PH; c->MaxQueryPerChunk = ph.d.Qpc; c->FinishedQueryNum = ph.fqn;
   return 0;
 }
+extern "C" uint64_t pm_batchpir_max_set_size(pm_batchpir* h) {
+  uint64_t m = 0;
+  if (h) for (const PartHost& p : h->e.parts) m = std::max<uint64_t>(m, p.d.SS);
+  return m;
+}
+// The server role: PianoPIRServer.PrivateQuery (pir.go:65-88)
+// of nq client-supplied offset sets, each over the partition it names.  Reads
+// the handle's DB (or its packed row image) and nothing of the client.
+extern "C" int pm_batchpir_server_answer(pm_batchpir* h, const uint32_t* parts, const uint32_t* offsets,
+                                         uint64_t stride, uint64_t nq, uint64_t* out) {
+  constexpr uint64_t kChunk = 65536;   // sets per upload / launch / download
+  if (nq == 0) return 0;
+  if (!h || !parts || !offsets || !out) return fail(PM_EINVAL, "NULL argument");
+  Engine* g = &h->e;
+  pm_ctx* c = g->ctx;
+  const uint64_t E = g->E;
+  if (stride < pm_batchpir_max_set_size(h)) return fail(PM_EINVAL, "stride must be >= the largest SetSize");
+  if (stride >> 32) return fail(PM_EINVAL, "stride must be < 2^32");
+  // every set is checked before any HIP call; the rows each chunk gathers are counted on the way
+  std::vector<uint64_t> gathered((nq + kChunk - 1) / kChunk, 0);
+  for (uint64_t s = 0; s < nq; ++s) {
+    const uint64_t p = parts[s];
+    if (p >= g->P) return fail(PM_EINVAL, "partition out of range: set " + std::to_string(s));
+    if (!g->parts[p].owned) return fail(PM_EINVAL, "partition not on this shard: set " + std::to_string(s));
+    const PmPart& d = g->parts[p].d;
+    const uint32_t* o = offsets + s * stride;
+    uint64_t rows = 0;
+    for (uint64_t i = 0; i < d.SS; ++i) {
+      if (o[i] >= d.CS) return fail(PM_EINVAL, "offset out of range: set " + std::to_string(s) + ", chunk " + std::to_string(i));
+      rows += i * d.CS + o[i] < d.N;
+    }
+    gathered[s / kChunk] += rows;
+  }
+  HIPCHK(hipSetDevice(c->device));
+  if (!g->srv_parts_up) {
+    std::vector<PmSrvPart> v(g->P);
+    for (uint64_t p = 0; p < g->P; ++p) {
+      const PmPart& d = g->parts[p].d;
+      v[p] = PmSrvPart{d.N, d.row0, d.CS, d.SS};
+    }
+    CHK(g->srv_parts.reserve(g->P * sizeof(PmSrvPart)));
+    HIPCHK(hipMemcpy(g->srv_parts.p, v.data(), g->P * sizeof(PmSrvPart), hipMemcpyHostToDevice));
+    g->srv_parts_up = true;
+  }
+  const uint64_t cap = std::min(nq, kChunk);
+  CHK(g->qoffs.reserve(cap * stride * 4 + cap * 4));   // the chunk's sets, then their partitions
+  CHK(g->ans_srv.reserve(cap * E * 8));
+  const uint64_t* const dbp = g->apk_nseg ? g->apk->as<uint64_t>() : nullptr;
+  const double row_bytes = dbp ? g->apk_nseg * 16.0 : (double)(E & ~3ull) * 8;
+  for (uint64_t s0 = 0; s0 < nq; s0 += kChunk) {
+    const uint64_t n = std::min(kChunk, nq - s0);
+    uint32_t* const qpart = g->qoffs.as<uint32_t>() + cap * stride;
+    HIPCHK(hipMemcpyAsync(g->qoffs.p, offsets + s0 * stride, n * stride * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(qpart, parts + s0, n * 4, hipMemcpyHostToDevice, c->stream));
+    c->timed("server_answer", (double)gathered[s0 / kChunk] * row_bytes, [&] {
+      pmk::server_answer_parts(c->stream, g->srv_parts.as<PmSrvPart>(), qpart, g->qoffs.as<uint32_t>(), (uint32_t)n,
+                               (uint32_t)stride, g->db->as<uint64_t>(), dbp, g->apk_nseg, g->apk_cseg, (uint32_t)E,
+                               g->ans_srv.as<uint64_t>());
+    });
+    HIPCHK(hipGetLastError());
+    if (dbp) c->host_add(HT_SERVER_ANSWER_PACKED, 0.0);
+    HIPCHK(hipMemcpyAsync(out + s0 * E, g->ans_srv.p, n * E * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return 0;
+}
 extern "C" int pm_batchpir_export(pm_batchpir* h, uint64_t p, uint32_t* rk, uint64_t* pt, uint64_t* par,
                                   uint64_t* pp, uint64_t* bt, uint64_t* bpar, uint64_t* ri, uint64_t* rv,
                                   uint64_t* hist) {

@@ -241,7 +241,9 @@ struct Engine {
   hipEvent_t order_ev = nullptr;   // upload_parts_async: the client's stream's queued work, waited for on the device
   uint32_t gran_words = 0;
   std::vector<uint32_t> owned_list;   // owned partitions in order (owned_d holds their PmPart)
-  DevBuf qoffs, ans_srv;
+  DevBuf qoffs, ans_srv;   // the server role's offset sets (then their partitions) and answers, one chunk of a call
+  DevBuf srv_parts;        // pm_batchpir_server_answer: [P] PmSrvPart, uploaded by the first call (they never change)
+  bool srv_parts_up = false;
   StepBufs buf;   // the step's scratch (engine_step)
   std::vector<double> stamp_sum;   // PM_STAMPS builds: accumulated phase deltas
   uint64_t stamp_n = 0;

@@ -116,6 +116,13 @@ struct PmPart {
   // slices hold high halves only, 16 words per slice (k_fold_image).
   const PM_G uint64_t* img;
 };
+// The server's side of a partition, all that k_server_answer_parts reads of it
+// (pm_batchpir_server_answer): fixed when the handle is created, no client state.
+struct PmSrvPart {
+  uint64_t N;      // DBSize of this sub-PIR
+  uint64_t row0;   // its first row in the handle's DB
+  uint32_t CS, SS;
+};
 
 // tabT layout: chunk c of tag t at tile (c / 8, t), element c % 8 (16-B tiles of
 // 8 chunks; SetSize padded to a multiple of 8 with kSkip), so the writer of 8
@@ -493,6 +500,11 @@ uint32_t step_max_ss();
 uint32_t step_max_e();
 void server_answer(hipStream_t st, const PmPart* dpart, const uint32_t* offs, uint32_t nq,
                    uint32_t SS, const uint64_t* db, uint32_t E, uint64_t* out);
+// k_server_answer_parts: set s (offs + s * stride) over partition qpart[s] of sp.  dbp: the packed row image
+// (pk_nseg / pk_cseg as PmStep's), gathered instead of db when not null.
+void server_answer_parts(hipStream_t st, const PmSrvPart* sp, const uint32_t* qpart, const uint32_t* offs,
+                         uint32_t nq, uint32_t stride, const uint64_t* db, const uint64_t* dbp, uint32_t pk_nseg,
+                         uint32_t pk_cseg, uint32_t E, uint64_t* out);
 void l2_rows(hipStream_t st, const float* rows, uint64_t row_stride_floats, uint64_t nrows,
              const uint32_t* row_ids, const float* q, uint32_t dim, float* out, uint64_t seglen = 0);
 void ip_rows(hipStream_t st, const uint32_t* rows, uint64_t nrows, const uint32_t* q, uint32_t dim,

@@ -924,6 +924,89 @@ __global__ void __launch_bounds__(kBlock) k_server_answer(const PmPart* __restri
   for (uint32_t w = EX + threadIdx.x; w < E; w += kBlock) out[w] = 0;
 }
 
+// The same for a batch PIR's partitions (pm_batchpir_server_answer): set s is
+// answered over partition qpart[s], whose DB-side parameters (PmSrvPart: no
+// client state) it looks up itself, so one launch serves sets of partitions of
+// different length.  One workgroup per set, lanes = (row slice, 16-B segment)
+// as above, with kSrvFlight rows in flight per lane: a set is SetSize rows of
+// one partition (245 of 640 B at SIFT1M), enough for 256 lanes, and a remote
+// client's batch can be as small as one set per partition, which one wave per
+// set would leave with a quarter of the loads in flight.
+// rows / rw: the stored rows and their length in 64-bit words.  PK: the packed
+// row image (k_answer_pack_image; NSEG segments per row, the first cseg of
+// them eight coordinate high halves each, E % 4 == 0): the XOR of packed rows
+// is the packed XOR since every dropped half is zero, and the reducing lane
+// widens its segment back into the answer's words.
+constexpr uint32_t kSrvFlight = 4;
+template <int W, bool PK>
+__global__ void __launch_bounds__(kBlock) k_server_answer_parts(const PmSrvPart* __restrict__ sp,
+                                                                const uint32_t* __restrict__ qpart,
+                                                                const uint32_t* __restrict__ qoffs, uint32_t stride,
+                                                                const uint64_t* __restrict__ rows, uint32_t rw,
+                                                                uint32_t NSEG, uint32_t cseg, uint32_t E,
+                                                                uint64_t* __restrict__ ans) {
+  static_assert(!PK || W == 2, "packed rows are whole 16-B segments");
+  __shared__ uint64_t red[kBlock * 2];
+  const uint32_t s = blockIdx.x;
+  const PmSrvPart P = sp[qpart[s]];
+  const uint32_t* qo = qoffs + (uint64_t)s * stride;
+  const uint64_t* base = rows + P.row0 * rw;
+  uint64_t* out = ans + (uint64_t)s * E;
+  for (uint32_t seg0 = 0; seg0 < NSEG; seg0 += kBlock) {
+    const uint32_t nseg = min(NSEG - seg0, (uint32_t)kBlock);
+    const uint32_t nsl = kBlock / nseg;
+    const uint32_t sl = threadIdx.x / nseg, seg = seg0 + threadIdx.x % nseg;
+    uint64_t a0 = 0, a1 = 0;
+    if (sl < nsl) {
+      for (uint32_t i0 = sl; i0 < P.SS; i0 += kSrvFlight * nsl) {
+        uint64_t x0[kSrvFlight], x1[kSrvFlight];
+#pragma unroll
+        for (uint32_t u = 0; u < kSrvFlight; ++u) {
+          const uint32_t i = i0 + u * nsl;
+          x0[u] = 0; x1[u] = 0;
+          if (i >= P.SS) continue;
+          const uint64_t r = (uint64_t)i * P.CS + qo[i];
+          if (r >= P.N) continue;   // pir.go:75-77
+          const uint64_t* p = base + r * rw + (uint64_t)seg * W;
+          if (W == 2) {
+            const uint4 x = *reinterpret_cast<const uint4*>(p);
+            x0[u] = ((uint64_t)x.y << 32) | x.x;
+            x1[u] = ((uint64_t)x.w << 32) | x.z;
+          } else {
+            x0[u] = *p;
+          }
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kSrvFlight; ++u) { a0 ^= x0[u]; a1 ^= x1[u]; }
+      }
+    }
+    red[threadIdx.x * 2] = a0;
+    red[threadIdx.x * 2 + 1] = a1;
+    __syncthreads();
+    if (threadIdx.x < nseg) {
+      uint64_t x0 = 0, x1 = 0;
+      for (uint32_t k = 0; k < nsl; ++k) {
+        x0 ^= red[(k * nseg + threadIdx.x) * 2];
+        x1 ^= red[(k * nseg + threadIdx.x) * 2 + 1];
+      }
+      if (PK && seg < cseg) {   // half-word pair k of the segment: the high halves of 32-bit words 8 seg + 2 k, + 1
+        const uint32_t v[4] = {(uint32_t)x0, (uint32_t)(x0 >> 32), (uint32_t)x1, (uint32_t)(x1 >> 32)};
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k)
+          out[4 * seg + k] = ((uint64_t)(v[k] & 0xffff0000u) << 32) | (uint64_t)(uint32_t)(v[k] << 16);
+      } else if (PK) {
+        out[4 * cseg + 2 * (seg - cseg)] = x0;
+        out[4 * cseg + 2 * (seg - cseg) + 1] = x1;
+      } else {
+        out[(uint64_t)seg * W] = x0;
+        if (W == 2) out[(uint64_t)seg * W + 1] = x1;
+      }
+    }
+    __syncthreads();
+  }
+  for (uint32_t w = (E & ~3u) + threadIdx.x; w < E; w += kBlock) out[w] = 0;
+}
+
 // ---------------------------------------------------------------------------
 // Distance kernels (graphann/l2_distance_amd64.s).
 // ---------------------------------------------------------------------------
@@ -1302,6 +1385,20 @@ void server_answer(hipStream_t st, const PmPart* d, const uint32_t* offs, uint32
     hipLaunchKernelGGL(k_server_answer<2>, dim3(nq), dim3(kBlock), 0, st, d, offs, SS, db, E, out);
   else
     hipLaunchKernelGGL(k_server_answer<1>, dim3(nq), dim3(kBlock), 0, st, d, offs, SS, db, E, out);
+}
+void server_answer_parts(hipStream_t st, const PmSrvPart* sp, const uint32_t* qpart, const uint32_t* offs,
+                         uint32_t nq, uint32_t stride, const uint64_t* db, const uint64_t* dbp, uint32_t pk_nseg,
+                         uint32_t pk_cseg, uint32_t E, uint64_t* out) {
+  const uint32_t EX = E & ~3u;
+  if (dbp)
+    hipLaunchKernelGGL((k_server_answer_parts<2, true>), dim3(nq), dim3(kBlock), 0, st, sp, qpart, offs, stride, dbp,
+                       2 * pk_nseg, pk_nseg, pk_cseg, E, out);
+  else if (E % 2 == 0)
+    hipLaunchKernelGGL((k_server_answer_parts<2, false>), dim3(nq), dim3(kBlock), 0, st, sp, qpart, offs, stride, db,
+                       E, EX / 2, 0u, E, out);
+  else
+    hipLaunchKernelGGL((k_server_answer_parts<1, false>), dim3(nq), dim3(kBlock), 0, st, sp, qpart, offs, stride, db,
+                       E, EX, 0u, E, out);
 }
 void l2_rows(hipStream_t st, const float* rows, uint64_t stride, uint64_t nrows, const uint32_t* ids,
              const float* q, uint32_t dim, float* out, uint64_t seglen) {
