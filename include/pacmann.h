@@ -335,6 +335,54 @@ int  pm_batchpir_server_answer(pm_batchpir* h, const uint32_t* parts /* nq */,
                                const uint32_t* offsets /* nq x stride */, uint64_t stride,
                                uint64_t nq, uint64_t* out /* nq x DBEntrySize */);
 uint64_t pm_batchpir_max_set_size(pm_batchpir* h);   /* max SetSize over the handle's partitions; 0 for NULL */
+/* The client role alone: one SimpleBatchPianoPIR.Query
+ * (batch-pir.go:170-248) cut at the wire.  pm_batchpir_client_begin buckets the
+ * ids, runs the step's hint search and resolution (Client.Query up to
+ * pir.go:444) and returns, in sub-query order (partition-major, slot order
+ * within a partition), one offset set per sub-query that reaches
+ * server.PrivateQuery: parts[s] its partition, offsets[s*stride .. +SetSize(P))
+ * the set with the programmed point and the replacement substituted
+ * (pir.go:430-439; a dummy's random set, :363-371), [SetSize(P), stride) zero;
+ * *nq sets in all.  Cached, duplicate, failed and skipped sub-queries send
+ * nothing.  The arrays are pm_batchpir_server_answer's input on any handle over
+ * the same DB.  pm_batchpir_client_finish takes that call's nq x DBEntrySize
+ * answers (a dummy set's row is not read) and does the rest of Query: decode,
+ * hint refresh, localCache, the responses (out, ok as pm_batchpir_query_ok),
+ * the batch counters and the re-preprocessing trigger, which preprocesses over
+ * the handle's own DB as Query does.  Results, counters and exported state
+ * are bit-identical to pm_batchpir_query_ok of the same ids.
+ * begin opens a split query on the handle and finish closes it; the calls
+ * alternate strictly.  While one is open every other client call on the handle
+ * (pm_batchpir_query*, a group query it is a member of, begin, the graph calls
+ * over pm_graph_pir, pm_batchpir_dummy_preprocessing) fails with PM_EINVAL, "a
+ * split query is open", and changes nothing; pm_batchpir_preprocessing is
+ * allowed and closes it (pm_batchpir_group_preprocessing of a group with such a
+ * member and pm_graph_group_preprocess are refused like the other calls:
+ * preprocess the handle itself); pm_batchpir_server_answer is always allowed.  There is
+ * NO ABORT: when begin returns, the resolver has already advanced the hints'
+ * tags and program points, the histograms and FinishedQueryNum, so the only
+ * ways on are finish and a preprocessing.
+ * PM_EINVAL before any HIP call and with nothing changed: a NULL argument; an
+ * id >= DBSize; stride < pm_batchpir_max_set_size(h); cap <
+ * pm_batchpir_client_max_sets(h, n); n / PartitionNum equal to 0 or above the
+ * step's sub-queries per partition; finish with no open query or with nq not
+ * the value begin returned; a shard handle (nshards > 1); DBEntrySize > 256
+ * words or a SetSize > 1,024.  begin also refuses, with "partition at its query
+ * budget: preprocess first" and nothing changed, a batch that would take a
+ * partition to MaxQueryNum (where Query re-preprocesses mid-batch,
+ * pir.go:527-530): preprocess and call begin again; with n / PartitionNum <= 2
+ * this cannot occur.  A HIP failure inside begin (PM_EHIP / PM_ENOMEM) is not
+ * such a refusal: the buffers are reserved before anything moves, but a failed
+ * launch or copy can leave the dummy counters or the hints advanced; preprocess
+ * the handle before using it again.  Timing names: "client_sets", "client_finish" (level 1),
+ * "host_client_begin", "host_client_finish". */
+uint64_t pm_batchpir_client_max_sets(pm_batchpir* h, uint64_t n);   /* PartitionNum * (n / PartitionNum); 0 for NULL */
+int  pm_batchpir_client_begin(pm_batchpir* h, const uint64_t* ids, uint64_t n,
+                              uint32_t* parts /* cap */, uint32_t* offsets /* cap x stride */,
+                              uint64_t stride, uint64_t cap, uint64_t* nq);
+int  pm_batchpir_client_finish(pm_batchpir* h, const uint64_t* answers /* nq x DBEntrySize */,
+                               uint64_t nq, uint64_t* out /* n x DBEntrySize */,
+                               uint8_t* ok /* n, nullable */);
 /* The speculation record of this handle's last step (test hook), where the
  * fused step kernel (k_step, "host_path_step") ran it on a context created with
  * PM_STEP_SPEC=1: *nsub words in sub-query order (partition-major, qn slots per

@@ -126,6 +126,9 @@ SIGNATURES = {
     "pm_batchpir_step_spec": (C.c_int, [vp, C.POINTER(C.c_uint32), u64, C.POINTER(u64)]),
     "pm_batchpir_server_answer": (C.c_int, [vp, u32p, u32p, u64, u64, u64p]),
     "pm_batchpir_max_set_size": (u64, [vp]),
+    "pm_batchpir_client_max_sets": (u64, [vp, u64]),
+    "pm_batchpir_client_begin": (C.c_int, [vp, u64p, u64, u32p, u32p, u64, u64, u64p]),
+    "pm_batchpir_client_finish": (C.c_int, [vp, u64p, u64, u64p, C.POINTER(C.c_uint8)]),
     "pm_pir_export": (C.c_int, [vp, u32p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "pm_batchpir_export": (C.c_int, [vp, u64, u32p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "pm_graph_create": (C.c_int, [vp, u64, u64, u64, f32p, u32p, C.c_int, C.c_int, u64, u64, C.POINTER(vp)]),
@@ -237,6 +240,16 @@ def hip_runtimes() -> set[str]:
     and events the first cannot use (pacmann_amd.shard refuses that case)."""
     with open("/proc/self/maps") as fh:
         return {ln.split()[-1] for ln in fh if "libamdhip64" in ln}
+
+
+# The open split query of each batch PIR handle (QueryBegin .. QueryFinish): handle address -> len(idx) of the
+# begin, i.e. the rows pm_batchpir_client_finish writes.  Kept per handle, not per wrapper object: several
+# wrappers can share one handle (PIRGraphInfo.PIR makes a new one on every access).
+_split_pending: dict[int, int] = {}
+
+
+def _handle_key(h):
+    return getattr(h, "value", h)
 
 
 def _check(rc: int):
@@ -546,6 +559,7 @@ class SimpleBatchPianoPIR:
 
     def __del__(self):
         if getattr(self, "h", None) and self._owned:
+            _split_pending.pop(_handle_key(self.h), None)   # the address may be handed out again
             lib().pm_batchpir_destroy(self.h)
         self.h = None
 
@@ -563,6 +577,7 @@ class SimpleBatchPianoPIR:
 
     def Preprocessing(self):
         _check(lib().pm_batchpir_preprocessing(self.h))
+        _split_pending.pop(_handle_key(self.h), None)   # it closes an open split query
 
     def DummyPreprocessing(self):
         _check(lib().pm_batchpir_dummy_preprocessing(self.h))
@@ -646,6 +661,49 @@ class SimpleBatchPianoPIR:
         _check(lib().pm_batchpir_server_answer(self.h, _p(p, u32p), _p(o, u32p), o.shape[1], o.shape[0],
                                                _p(out, u64p)))
         return out
+
+    def QueryBegin(self, idx):
+        """The client half of a two-party Query, first call (pm_batchpir_client_begin):
+        buckets idx, runs the step's hint search and resolution, and returns
+        (parts [nq] uint32, offsets [nq, max_set_size] uint32): the sets to
+        hand to the server's ServerAnswer, one per sub-query that sends one.
+        Opens a split query: the next client call must be QueryFinish (or
+        Preprocessing).  There is no abort."""
+        ids = _u64(idx).ravel()
+        cap = int(lib().pm_batchpir_client_max_sets(self.h, len(ids)))
+        stride = self.max_set_size
+        parts = np.zeros(cap, dtype=np.uint32)
+        offs = np.zeros((cap, stride), dtype=np.uint32)
+        nq = u64(0)
+        _check(lib().pm_batchpir_client_begin(self.h, _p(ids, u64p), len(ids), _p(parts, u32p), _p(offs, u32p),
+                                              stride, cap, C.byref(nq)))
+        _split_pending[_handle_key(self.h)] = len(ids)
+        return parts[:nq.value], offs[:nq.value]
+
+    def QueryFinish(self, answers):
+        """The second call (pm_batchpir_client_finish): answers [nq, DBEntrySize]
+        uint64, row s the server's answer to set s of QueryBegin.  Returns
+        (responses [len(idx), DBEntrySize] uint64, ok [len(idx)] bool) as
+        QueryWithMask of the same ids would.  The output is sized from what
+        QueryBegin recorded for the handle (any wrapper object of it will do,
+        e.g. two PIRGraphInfo.PIR accesses); with nothing recorded the call is
+        refused here, never made with a guessed size."""
+        a = np.asarray(answers)
+        if a.dtype != np.uint64:
+            raise TypeError("answers must be uint64")
+        if a.ndim != 2 or a.shape[1] != self.E:
+            raise ValueError("answers must be [nq, DBEntrySize]")
+        a = np.ascontiguousarray(a)
+        key = _handle_key(self.h)
+        if key not in _split_pending:
+            raise RuntimeError("libpacmann error -1: no split query is open (no QueryBegin on this handle)")
+        n = _split_pending[key]
+        out = np.zeros((max(n, 1), self.E), dtype=np.uint64)   # (never a NULL pointer: the library names the real fault)
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        _check(lib().pm_batchpir_client_finish(self.h, _p(a, u64p) if a.shape[0] else None, a.shape[0], _p(out, u64p),
+                                               ok.ctypes.data_as(C.POINTER(C.c_uint8))))
+        _split_pending.pop(key, None)
+        return out[:n], ok[:n].astype(bool)
 
     def LocalStorageSize(self) -> float:
         return self.stats()["LocalStorage"]
@@ -771,6 +829,7 @@ class PIRGraphInfo:
         return ids.astype(np.int64), vec, nb
 
     def Preprocess(self):
+        _split_pending.pop(lib().pm_graph_pir(self.h), None)   # the session's client is replaced
         _check(lib().pm_graph_preprocess(self.h))
 
     @property

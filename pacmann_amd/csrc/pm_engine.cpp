@@ -777,7 +777,11 @@ int step_chain(pm_ctx* c, StepBufs& B, PmStep& S, const pmk::StepShape& shape, u
 #endif
   run(pmk::STAGE_MATCH, "hint_match", (double)nreal * shape.maxPH);
   run(pmk::STAGE_RESOLVE, "resolve", 0);
-  if (after_resolve) CHK(after_resolve());
+  if (after_resolve) {
+    const int r = after_resolve();
+    if (r == kChainStop) return 0;   // the client role: the answer is another call's (pm_batchpir_client_finish)
+    CHK(r);
+  }
   run(pmk::STAGE_GATHER, "gather", ans_bytes);
 #ifdef PM_ANSWER_STAMPS
   LaunchStamps as;   // {nsub} + nsub x 8 stamps per answer kernel (PM_ANSWER_STAMPS)
@@ -792,12 +796,15 @@ int step_chain(pm_ctx* c, StepBufs& B, PmStep& S, const pmk::StepShape& shape, u
   return 0;
 }
 
-int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
-  auto t_begin = Clock::now();
+// The descriptor of the engine's own step over g->subs / g->sb (at least one
+// sub-query), its scratch reserved, and what pmk::step_plan chooses from.
+static int step_setup(Engine* g, const float* q_dev, uint32_t dim, PmStep& S, pmk::StepShape& shape, uint32_t& nreal,
+                      double& ans_bytes) {
   pm_ctx* c = g->ctx;
+#ifdef PM_STAMPS
   hipStream_t st = c->stream;
+#endif
   const uint32_t nsub = (uint32_t)g->subs.size();
-  if (nsub == 0) return 0;
   const uint64_t E = g->E;
   const uint32_t words = (g->maxPH + 63) / 64, cblk = pmk::step_match_blocks(g->maxPH);
   StepBufs& B = g->buf;
@@ -808,7 +815,7 @@ int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
   char* dh = B.desc_h.as<char>();
   memcpy(dh, g->subs.data(), dsub);
   memcpy(dh + dsub, g->sb.data(), (g->P + 1) * 4);
-  PmStep S{};
+  S = PmStep{};
   S.parts = g->parts_d.as<PmPart>();
   S.subs_h = (const PmSub*)dh;
   S.sb_h = (const uint32_t*)(dh + dsub);
@@ -834,9 +841,9 @@ int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
   S.token = next_token(g->step_token);
   step_read_window(S, g->pf_off, g->pf_len, E);
   S.rows_partial = host_rows_partial(c, g->rows_partial);
-  uint32_t nreal = 0;
+  nreal = 0;
   for (auto& x : g->subs) nreal += x.kind == SUB_REAL;
-  pmk::StepShape shape{};
+  shape = pmk::StepShape{};
   shape.np = (uint32_t)g->P; shape.nsub = nsub; shape.maxPH = g->maxPH; shape.maxSS = g->maxSS; shape.E = (uint32_t)E; shape.ph8 = g->ph8;
   for (uint64_t p = 0; p < g->P; ++p) {
     const uint32_t n = g->sb[p + 1] - g->sb[p];
@@ -849,9 +856,24 @@ int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
     memcpy(S.subs_a, g->subs.data(), dsub);
     memcpy(S.sb_a, g->sb.data(), (g->P + 1) * 4);
   }
-  double ans_bytes = 0;
+  ans_bytes = 0;
   for (auto& x : g->subs)
     if (x.kind == SUB_REAL || x.kind == SUB_DUMMY) ans_bytes += answer_bytes(g->parts[x.part].d, E);
+  return 0;
+}
+
+int engine_step(Engine* g, const float* q_dev, uint32_t dim) {
+  auto t_begin = Clock::now();
+  pm_ctx* c = g->ctx;
+  hipStream_t st = c->stream;
+  const uint32_t nsub = (uint32_t)g->subs.size();
+  if (nsub == 0) return 0;
+  PmStep S;
+  pmk::StepShape shape;
+  uint32_t nreal;
+  double ans_bytes;
+  CHK(step_setup(g, q_dev, dim, S, shape, nreal, ans_bytes));
+  StepBufs& B = g->buf;
   // One launch (k_step) when the step fits it, else the three kernels (pmk::step_plan).
   std::function<int()> dump_res;
   if (c->debug_sync) dump_res = [&]() -> int {   // validate every resolution record before k_answer consumes it
@@ -1076,7 +1098,11 @@ extern "C" int pm_batchpir_create_client(pm_ctx* ctx, pm_batchpir* server, uint6
 }
 extern "C" void pm_batchpir_destroy(pm_batchpir* h) { delete h; }
 namespace pmh {
+int split_guard(const Engine* g) {
+  return g->split.open ? fail(PM_EINVAL, "a split query is open") : 0;
+}
 int batch_prep(Engine* g) {   // Preprocessing (batch-pir.go:119-155)
+  g->split.open = false;   // every hint is rebuilt: an open split query (pm_batchpir_client_begin) has nothing left to finish
   g->FBN = 0; g->QMIP = 0;
   auto t0 = std::chrono::steady_clock::now();
   CHK(engine_prep(g, 0, g->P));
@@ -1088,6 +1114,7 @@ int batch_prep(Engine* g) {   // Preprocessing (batch-pir.go:119-155)
 }  // namespace pmh
 extern "C" int pm_batchpir_preprocessing(pm_batchpir* h) { return batch_prep(&h->e); }
 extern "C" int pm_batchpir_dummy_preprocessing(pm_batchpir* h) {   // batch-pir.go:157-166
+  CHK(split_guard(&h->e));
   h->e.skipPrep = true;
   CHK(engine_prep(&h->e, 0, h->e.P));
   record_stats(&h->e, 0);
@@ -1107,6 +1134,7 @@ namespace pmh {
 int batch_query(Engine* g, const uint64_t* idx, uint64_t n, uint64_t* out, const float* q_dev,
                        uint32_t dim, float* dist_out, const uint64_t** rows_out,
                        uint8_t* ok) {
+  CHK(split_guard(g));
   auto t = Clock::now();
   int r = batch_query_impl(g, idx, n, out, q_dev, dim, dist_out, rows_out, ok);
   g->ctx->host_add(HT_BATCH_QUERY, ms_since(t));
@@ -1128,6 +1156,7 @@ namespace pmh {
 //   bq_tail      FinishedBatchNum / QueriesMadeInPartition and the
 //                re-preprocessing trigger (:238-247).
 int bq_prepare(Engine* g, const uint64_t* idx, uint64_t n, bool* fast) {
+  CHK(split_guard(g));   // (the entry points check first, before they change anything)
   const uint64_t E = g->E, P = g->P;
   CHK(ensure_host_cache(g));
   if (g->zero_row.size() != E) g->zero_row.assign(E, 0);
@@ -1280,6 +1309,7 @@ extern "C" int pm_batchpir_query_dev(pm_batchpir* h, const uint64_t* ids, uint64
                                      void* stream) {
   Engine* g = &h->e;
   if (n && (!ids || !dev_out)) return fail(PM_EINVAL, "NULL argument");
+  CHK(split_guard(g));
   auto t = Clock::now();
   const int r = query_dev_impl(g, ids, n, dev_out, (hipStream_t)stream);
   g->ctx->host_add(HT_BATCH_QUERY, ms_since(t));
@@ -1440,6 +1470,119 @@ extern "C" int pm_batchpir_server_answer(pm_batchpir* h, const uint32_t* parts, 
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return 0;
+}
+// The client role: SimpleBatchPianoPIR.Query cut at the wire.
+// begin is Query up to server.PrivateQuery (bucketing, the step's hint search
+// and resolution, the sets out); finish is the rest of it over the server's
+// answers (the answer kernels' epilogue, the host mirrors, the responses, the
+// batch counters and trigger).
+extern "C" uint64_t pm_batchpir_client_max_sets(pm_batchpir* h, uint64_t n) {
+  return h ? h->e.P * (n / h->e.P) : 0;
+}
+extern "C" int pm_batchpir_client_begin(pm_batchpir* h, const uint64_t* ids, uint64_t n, uint32_t* parts,
+                                        uint32_t* offsets, uint64_t stride, uint64_t cap, uint64_t* nq) {
+  if (!h || !ids || !parts || !offsets || !nq) return fail(PM_EINVAL, "NULL argument");
+  Engine* g = &h->e;
+  pm_ctx* c = g->ctx;
+  const uint64_t E = g->E, P = g->P, qn = n / P;
+  CHK(split_guard(g));
+  if (g->nshards > 1) return fail(PM_EINVAL, "the client role is not built for shard handles");
+  if (E > pmk::client_max_e() || g->maxSS > pmk::client_max_ss())
+    return fail(PM_EINVAL, "the client role serves DBEntrySize <= 256 words and SetSize <= 1024");
+  for (uint64_t i = 0; i < n; ++i)
+    if (ids[i] >= g->N) return fail(PM_EINVAL, "id " + std::to_string(ids[i]) + " >= DBSize");
+  if (stride < g->maxSS) return fail(PM_EINVAL, "stride must be >= the largest SetSize");
+  if (qn == 0 || qn > pmk::step_max_sub_per_part())
+    return fail(PM_EINVAL, "n / PartitionNum must be in [1, " + std::to_string(pmk::step_max_sub_per_part()) + "]");
+  if (cap < P * qn) return fail(PM_EINVAL, "cap must be >= pm_batchpir_client_max_sets");
+  auto t_begin = Clock::now();
+  {   // bq_prepare's budget rule, before anything moves: the first qn ids of a partition are its sub-queries
+    std::vector<uint64_t> cnt(P, 0);
+    for (uint64_t i = 0; i < n; ++i) ++cnt[g->part_of(ids[i])];
+    for (uint64_t p = 0; p < P; ++p)
+      if (g->parts[p].fqn + std::min(cnt[p], qn) >= g->parts[p].maxq64)
+        return fail(PM_EINVAL, "partition at its query budget: preprocess first");
+  }
+  // every buffer of the call is reserved before the bucketing moves anything (the dummy counters): the step has
+  // P * qn sub-queries, as every partition is this handle's
+  Engine::SplitQuery& Q = g->split;
+  const uint32_t qw = (g->maxSS + 3) & ~3u;
+  const size_t set_bytes = (size_t)P * qn * qw * 4, down = set_bytes + (size_t)P * qn * 4;
+  HIPCHK(hipSetDevice(c->device));
+  CHK(Q.sets_d.reserve(down));
+  CHK(Q.sets_h.reserve(down));
+  CHK(g->buf.reserve((uint32_t)(P * qn), (uint32_t)P, (g->maxPH + 63) / 64, pmk::step_match_blocks(g->maxPH), E));
+  CHK(g->buf.desc_h.reserve(P * qn * sizeof(PmSub) + (P + 1) * 4));
+  CHK(g->buf.out_h.reserve(step_out_bytes((uint32_t)(P * qn), E)));
+  bool fast = false;
+  CHK(bq_prepare(g, ids, n, &fast));
+  const uint32_t nsub = (uint32_t)g->subs.size();
+  if (!fast || nsub != P * qn) return fail(PM_EINVAL, "the batch does not fit one step");   // (excluded by the checks above)
+  PmStep& S = Q.S;
+  pmk::StepShape shape;
+  uint32_t nreal;
+  double ans_bytes;
+  CHK(step_setup(g, nullptr, 0, S, shape, nreal, ans_bytes));
+  shape.unfused = true;   // the hint search and the resolution as launches of their own, whatever the context says
+  shape.no_split = true;
+  uint32_t* const modes_d = Q.sets_d.as<uint32_t>() + (size_t)nsub * qw;
+  CHK(step_chain(c, g->buf, S, shape, nreal, 0, [&]() -> int {
+    c->timed("client_sets", (double)down, [&] { pmk::client_sets(c->stream, S, Q.sets_d.as<uint32_t>(), modes_d, qw); });
+    return kChainStop;
+  }));
+  HIPCHK(hipGetLastError());
+  // from here on the hints have moved: the query is open whatever happens to the copy
+  Q.open = true;
+  Q.ids.assign(ids, ids + n);
+  Q.map.assign(nsub, ~0u);
+  Q.nq = 0;
+  HIPCHK(hipMemcpyAsync(Q.sets_h.p, Q.sets_d.p, down, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  // the sending rows, compacted on the way out
+  const uint32_t* const sets = Q.sets_h.as<uint32_t>();
+  const uint32_t* const modes = sets + (size_t)nsub * qw;
+  uint64_t k = 0;
+  for (uint32_t s = 0; s < nsub; ++s) {
+    if (!pmk::client_mode_sends(modes[s])) continue;
+    const uint32_t SS = g->parts[g->subs[s].part].d.SS;
+    uint32_t* o = offsets + k * stride;
+    memcpy(o, sets + (size_t)s * qw, (size_t)SS * 4);
+    memset(o + SS, 0, (size_t)(stride - SS) * 4);
+    parts[k] = g->subs[s].part;
+    if (pmk::client_mode_reads(modes[s])) Q.map[s] = (uint32_t)k;
+    ++k;
+  }
+  Q.nq = k;
+  *nq = k;
+  c->host_add(HT_CLIENT_BEGIN, ms_since(t_begin));
+  return 0;
+}
+extern "C" int pm_batchpir_client_finish(pm_batchpir* h, const uint64_t* answers, uint64_t nq, uint64_t* out,
+                                         uint8_t* ok) {
+  if (!h || !out || (!answers && nq)) return fail(PM_EINVAL, "NULL argument");
+  Engine* g = &h->e;
+  pm_ctx* c = g->ctx;
+  Engine::SplitQuery& Q = g->split;
+  if (!Q.open) return fail(PM_EINVAL, "no split query is open");
+  if (nq != Q.nq) return fail(PM_EINVAL, "nq is not the number of sets pm_batchpir_client_begin returned");
+  auto t_begin = Clock::now();
+  const uint64_t E = g->E, n = Q.ids.size();
+  const PmStep& S = Q.S;
+  const uint32_t nsub = S.nsub;
+  HIPCHK(hipSetDevice(c->device));
+  CHK(Q.ans_d.reserve(std::max<uint64_t>(1, nq) * E * 8));
+  CHK(Q.map_d.reserve((size_t)nsub * 4));
+  Q.open = false;   // no abort: a failure below leaves nothing to finish either
+  if (nq) HIPCHK(hipMemcpyAsync(Q.ans_d.p, answers, nq * E * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(Q.map_d.p, Q.map.data(), (size_t)nsub * 4, hipMemcpyHostToDevice, c->stream));
+  c->timed("client_finish", (double)nq * E * 8,
+           [&] { pmk::client_finish(c->stream, S, Q.ans_d.as<uint64_t>(), Q.map_d.as<uint32_t>()); });
+  g->step_seq = c->record_done(c->stream);
+  HIPCHK(hipGetLastError());
+  CHK(wait_and_post(g, S, nsub, t_begin));
+  bq_emit_fast(g, Q.ids.data(), n, out, nullptr, nullptr, ok);
+  c->host_add(HT_CLIENT_FINISH, ms_since(t_begin));
+  return bq_tail(g, n);
 }
 extern "C" int pm_batchpir_export(pm_batchpir* h, uint64_t p, uint32_t* rk, uint64_t* pt, uint64_t* par,
                                   uint64_t* pp, uint64_t* bt, uint64_t* bpar, uint64_t* ri, uint64_t* rv,

@@ -36,9 +36,11 @@ int wait_step(pm_ctx* c, const PmOutHdr* hdr, uint32_t nsub, uint32_t token, con
               size_t row_bytes, size_t pf_off, size_t pf_len, uint64_t seq, pm_ctx* sc = nullptr);
 void post_results(Engine* g, PmOutHdr* hdr, uint64_t* rows, uint32_t nsub, uint32_t base,
                   uint32_t token);
+constexpr int kChainStop = 1 << 30;   // after_resolve's return value that ends the chain there, with success
 int step_chain(pm_ctx* c, StepBufs& B, PmStep& S, const pmk::StepShape& shape, uint32_t nreal, double ans_bytes,
                const std::function<int()>& after_resolve = {});
 int engine_step(Engine* g, const float* q_dev, uint32_t dim);
+int split_guard(const Engine* g);   // PM_EINVAL "a split query is open" while the engine has one
 void print_stamps(const Engine& e);
 void record_stats(Engine* g, double t);
 int batch_prep(Engine* g);
@@ -244,6 +246,19 @@ struct Engine {
   DevBuf qoffs, ans_srv;   // the server role's offset sets (then their partitions) and answers, one chunk of a call
   DevBuf srv_parts;        // pm_batchpir_server_answer: [P] PmSrvPart, uploaded by the first call (they never change)
   bool srv_parts_up = false;
+  // The client role's split query (pm_batchpir_client_begin / _finish): between the two
+  // calls the step's descriptor (its scratch is `buf`, its host view subs / sb / sub_gid / resp_map), the
+  // caller's ids and each sub-query's answer row (~0u: it sent no set).  Buffers of its own: qoffs /
+  // ans_srv are the server call's, which may run on this handle in between.
+  struct SplitQuery {
+    bool open = false;
+    PmStep S{};
+    uint64_t nq = 0;
+    std::vector<uint64_t> ids;
+    std::vector<uint32_t> map;
+    DevBuf sets_d, ans_d, map_d;   // [nsub][qw] sets then [nsub] modes; [nq][E] answers; [nsub] map
+    HostBuf sets_h;                // the sets and modes, down
+  } split;
   StepBufs buf;   // the step's scratch (engine_step)
   std::vector<double> stamp_sum;   // PM_STAMPS builds: accumulated phase deltas
   uint64_t stamp_n = 0;

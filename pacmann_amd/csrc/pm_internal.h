@@ -498,6 +498,17 @@ inline bool step_answer_packed(const PmStep& S, const StepPlan& plan, int stage)
 uint32_t step_max_sub_per_part();
 uint32_t step_max_ss();
 uint32_t step_max_e();
+// The client role of a two-party round (pm_batchpir_client_begin / _finish), over a step whose hint search
+// and resolution have run (S.res).  k_client_sets: sub-query s's answer mode into modes[s] and, where it
+// gathers rows, its query set as u32 into sets[s][0 .. qw) (qw a multiple of 4, zero past SetSize).
+// k_client_finish: the answer's epilogue with sub-query s's gathered row read from answers[map[s]]
+// (E words each; map[s] = ~0u: no set was sent).  Shapes up to client_max_ss() / client_max_e().
+void client_sets(hipStream_t st, const PmStep& S, uint32_t* sets, uint32_t* modes, uint32_t qw);
+void client_finish(hipStream_t st, const PmStep& S, const uint64_t* answers, const uint32_t* map);
+bool client_mode_sends(uint32_t mode);   // a mode word of k_client_sets whose sub-query sends its set
+bool client_mode_reads(uint32_t mode);   // ... and whose answer row k_client_finish reads (not a dummy's)
+uint32_t client_max_ss();
+uint32_t client_max_e();
 void server_answer(hipStream_t st, const PmPart* dpart, const uint32_t* offs, uint32_t nq,
                    uint32_t SS, const uint64_t* db, uint32_t E, uint64_t* out);
 // k_server_answer_parts: set s (offs + s * stride) over partition qpart[s] of sp.  dbp: the packed row image

@@ -2772,6 +2772,76 @@ __global__ void __launch_bounds__(kStepBlock) k_step(PmStep S) {
   TS(2);
 }
 
+// ---- the client role of a two-party round -----------------
+// pm_batchpir_client_begin / _finish cut the step at the wire: after the hint
+// search and the resolution, k_client_sets hands out the query sets the answer
+// would gather (set_range's values), and k_client_finish is the answer's
+// epilogue over the rows a remote server XORed for them.  Shapes: k_answer_s's
+// (SetSize <= kSmallSS, entries <= kSmallE words).
+constexpr int kClientNT = 128;
+static_assert(kSmallSS % 4 == 0, "k_client_sets stores whole 16-B lanes");
+// One workgroup per sub-query: its answer mode into modes[s] and, where that
+// mode gathers rows, its set widened to u32 into sets[s][0 .. qw) (qw a
+// multiple of 4 in [SetSize, kSmallSS]; places past SetSize zero).
+__global__ void __launch_bounds__(kClientNT) k_client_sets(PmStep S, uint32_t* sets_, uint32_t* modes_, uint32_t qw) {
+  PM_G uint32_t* const sets = (PM_G uint32_t*)sets_;
+  PM_G uint32_t* const modes = (PM_G uint32_t*)modes_;
+  __shared__ __attribute__((aligned(16))) uint16_t qo[kSmallSS];
+  const uint32_t s = blockIdx.x, tid = threadIdx.x;
+  const PmSub sub = step_sub(S, s);
+  const PmRes r = S.res[s];
+  const uint32_t mode = answer_mode(r);
+  const PmPart& P = S.parts[sub.part];
+  if (tid == 0) modes[s] = mode;
+  if (!(mode == A_FINAL || mode == A_CHAINED || mode == A_DUMMY)) return;   // block-uniform
+  set_range<kClientNT>(P, sub, r, mode, qo, 0, P.SS);
+  __syncthreads();
+  PM_G uint4* const dst = reinterpret_cast<PM_G uint4*>(sets + (uint64_t)s * qw);
+  for (uint32_t i = 4 * tid; i < qw; i += 4 * kClientNT) {   // one 8-B LDS read, one 16-B store
+    const uint2 v = *reinterpret_cast<const uint2*>(qo + i);
+    uint4 o = make_uint4(v.x & 0xffffu, v.x >> 16, v.y & 0xffffu, v.y >> 16);
+    if (i + 0 >= P.SS) o.x = 0;
+    if (i + 1 >= P.SS) o.y = 0;
+    if (i + 2 >= P.SS) o.z = 0;
+    if (i + 3 >= P.SS) o.w = 0;
+    dst[i / 4] = o;
+  }
+}
+template <int NT>
+struct ClientFinishLds {
+  uint64_t red[NT * 2];
+  __attribute__((aligned(16))) RowBufT<kSmallE> row;
+  uint32_t s_last;
+};
+// One workgroup per sub-query: answer_role's work from the gathered row on,
+// the row being answers[map[s]] (map[s] kNone: no set was sent; a dummy's row
+// is not read).  The device functions of k_answer_p's turn, so the decode, the
+// refreshes, the publication and the chain arrival are that kernel's code.
+template <int W, int NT>
+__global__ void __launch_bounds__(NT, PM_ANSWER_WGS) k_client_finish(PmStep S, const uint64_t* answers_,
+                                                                     const uint32_t* map_) {
+  const PM_G uint64_t* const answers = (const PM_G uint64_t*)answers_;
+  const PM_G uint32_t* const map = (const PM_G uint32_t*)map_;
+  __shared__ ClientFinishLds<NT> L;
+  const uint32_t tid = threadIdx.x, E = S.E, EX = E & ~3u;
+  AnsQ a;
+  uint4 qpv;
+  ansp_record<W, NT>(S, blockIdx.x, a, qpv);   // (S.qw is 0 here: no pre-expanded set to load)
+  a.mode = answer_mode(a.r);
+  const uint32_t m = map[a.s];
+  ansp_decode_ops<W, NT>(S, a);
+  if ((a.mode == A_FINAL || a.mode == A_CHAINED) && m != kNone) {
+    typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+    const PM_G uint64_t* src = answers + (uint64_t)m * E;   // even E: rows are 16-B aligned
+    for (uint32_t w = W * tid; w < EX; w += W * NT) {
+      if (W == 2) *reinterpret_cast<u64x2*>(&L.row.w[w]) = *reinterpret_cast<const PM_G u64x2*>(src + w);
+      else L.row.w[w] = src[w];
+    }
+  }
+  __syncthreads();
+  ansp_epilogue<W, NT>(S, a, L);
+}
+
 }  // namespace pm
 
 namespace pmk {
@@ -2967,6 +3037,17 @@ void step_launch(hipStream_t st, const PmStep& S, const StepPlan& plan, int stag
     case FORM_ANSWER_G: PM_LAUNCH_W(k_answer); break;
   }
 }
+void client_sets(hipStream_t st, const PmStep& S, uint32_t* sets, uint32_t* modes, uint32_t qw) {
+  hipLaunchKernelGGL(k_client_sets, dim3(S.nsub), dim3(kClientNT), 0, st, S, sets, modes, qw);
+}
+void client_finish(hipStream_t st, const PmStep& S, const uint64_t* answers, const uint32_t* map) {
+  if (S.E % 2 == 0) hipLaunchKernelGGL((k_client_finish<2, kClientNT>), dim3(S.nsub), dim3(kClientNT), 0, st, S, answers, map);
+  else hipLaunchKernelGGL((k_client_finish<1, kClientNT>), dim3(S.nsub), dim3(kClientNT), 0, st, S, answers, map);
+}
+bool client_mode_sends(uint32_t mode) { return mode == A_FINAL || mode == A_CHAINED || mode == A_DUMMY; }
+bool client_mode_reads(uint32_t mode) { return mode == A_FINAL || mode == A_CHAINED; }
+uint32_t client_max_ss() { return kSmallSS; }
+uint32_t client_max_e() { return kSmallE; }
 uint32_t step_max_sub_per_part() { return kMaxSubPerPart; }
 uint32_t step_max_ss() { return kMaxSSLds; }
 uint32_t step_max_e() { return kMaxELds; }
