@@ -130,6 +130,8 @@ int pm_timing_enable(pm_ctx* ctx, int level);
  * "fault_drl_query" (tests): the device loop fails before queueing query
  * `value` (-1 off); its sessions are then unusable (every later call on them
  * returns PM_EINVAL: their host counters no longer match the device state).
+ * "stream_upload_only" (probes): 1 = pm_batchpir_prep_stream_rows stages and
+ * uploads its sub-windows without launching its kernels (0 default).
  * PM_EINVAL for an unknown name. */
 int pm_set_option(const char* name, int value);
 /* Which kernels an online step of a given shape launches: the answer of the one
@@ -383,6 +385,95 @@ int  pm_batchpir_client_begin(pm_batchpir* h, const uint64_t* ids, uint64_t n,
 int  pm_batchpir_client_finish(pm_batchpir* h, const uint64_t* answers /* nq x DBEntrySize */,
                                uint64_t nq, uint64_t* out /* n x DBEntrySize */,
                                uint8_t* ok /* n, nullable */);
+/* A SimpleBatchPianoPIR client with no DB on the device. */
+/* The deployment of the two roles above: keys and hints on the client's
+ * machine, rows on the server's.  The handle is a client in everything but the
+ * DB: every partition's parameters, keys, hint tables, counters, bucketing and
+ * localCache, with no rows, no fold image and no packed row image.  Its hints
+ * come from streamed preprocessings (below); pm_batchpir_export, _subconfig,
+ * _stats_get, _max_set_size, _client_max_sets, _client_begin and _client_finish
+ * work as on any client.  Every call that would read the DB fails with
+ * PM_EINVAL, "no DB on this handle", before any HIP call and with nothing
+ * changed: pm_batchpir_query*, pm_batchpir_preprocessing,
+ * pm_batchpir_server_answer, pm_batchpir_server_rows, pm_batchpir_create_client
+ * with it as server, pm_batchpir_group_create with it as a member.
+ * pm_batchpir_dummy_preprocessing stays allowed (it only zeroes hints).  Before
+ * its first completed stream (or dummy preprocessing) pm_batchpir_client_begin
+ * is refused: "not preprocessed".  Where pm_batchpir_client_finish's
+ * re-preprocessing trigger would preprocess, the handle cannot: finish returns
+ * its results, pm_batchpir_prep_due becomes 1 and the next begin is refused,
+ * "preprocessing due: stream it first"; after the stream the state and counters
+ * equal those of a pm_batchpir_create_client twin after the Query that
+ * re-preprocessed.  PM_EINVAL before any HIP call: ctx or out NULL, DBSize 0,
+ * DBEntryByteNum < 8, BatchSize < 2.  Device memory: the hint state, tabT, cur
+ * and, from the first stream on, two window slots of at most max(8 MiB, the
+ * largest chunk). */
+int pm_batchpir_create_remote(pm_ctx*, uint64_t DBSize, uint64_t DBEntryByteNum, uint64_t BatchSize,
+                              uint64_t FailureProbLog2, uint64_t seed, pm_batchpir** out);
+/* Streamed preprocessing: Piano's offline protocol, in which the DB passes the
+ * client once, chunk by chunk, and is never stored.  The three calls work on a
+ * remote handle and on any unsharded batch handle that has a DB (which it then
+ * ignores: the reference's UpdatePreprocessing surface); a shard handle
+ * (nshards > 1) is refused.
+ * pm_batchpir_prep_stream_begin is Client.Initialization (pir.go:203-255) of
+ * every partition: the next epoch's key, tags, program points, histogram and
+ * PRF tables, zero parities and replacement values, default replacement
+ * indices.  It opens a stream and closes an open split query, as
+ * pm_batchpir_preprocessing does.  While the stream is open every client call
+ * on the handle (pm_batchpir_client_begin / _finish, pm_batchpir_query*,
+ * pm_batchpir_dummy_preprocessing, group calls, the graph calls over
+ * pm_graph_pir) fails with PM_EINVAL, "a streamed preprocessing is open".  begin
+ * on an open stream abandons it and starts over with the NEXT epoch: this is
+ * how a dropped connection recovers, and it costs an epoch (the handle then
+ * equals a twin that preprocessed once more).  pm_batchpir_preprocessing on a
+ * handle with a DB also abandons an open stream.
+ * pm_batchpir_prep_stream_rows is PianoPIRClient.UpdatePreprocessing
+ * (pir.go:303-352) of chunks [chunk0, chunk0 + nchunks) of one partition in one
+ * call.  rows: that range's existing rows, partition rows [chunk0 * ChunkSize,
+ * min((chunk0 + nchunks) * ChunkSize, DBSize(P))), DBEntrySize words each
+ * (pm_batchpir_subconfig gives ChunkSize, SetSize and DBSize(P)); nrows must be
+ * their number, 0 (rows may be NULL) for chunks wholly past the partition's end,
+ * which exist because SetSize is rounded up to a multiple of 4 and still get
+ * their replacement indices.  The library zero-pads (pir.go:285-295).  Windows
+ * may come in any order, from any partition and in any sizes; every chunk of
+ * every partition exactly once.  rows is copied before the call returns and
+ * never retained; the call does not wait for the device, so the upload of one
+ * window overlaps the fold of the one before (sub-windows of whole chunks of at
+ * most max(8 MiB, one chunk) through two pinned slots).  PM_EINVAL before any
+ * HIP call and with nothing changed: a NULL handle, no open stream, "partition
+ * out of range", nchunks 0, chunk0 + nchunks > SetSize, a wrong nrows, NULL rows
+ * with nrows > 0, "chunk already delivered" for any overlap with an earlier
+ * window.
+ * pm_batchpir_prep_stream_end: PM_EINVAL "chunks missing: partition p, chunk c"
+ * (the first one) while a chunk is undelivered, the stream staying open;
+ * otherwise it waits for the device, closes the stream and resets the batch
+ * counters and counts PrepCount as pm_batchpir_preprocessing does.  The handle
+ * then equals, bit for bit in pm_batchpir_export and the counters of
+ * pm_batchpir_stats_get, a pm_batchpir_create_client twin of the same seed after
+ * the same number of pm_batchpir_preprocessing calls.  A HIP failure in rows or
+ * end leaves the stream unusable: begin again.
+ * Timing names: "prep_stream_fold", "prep_stream_repl" (level 1, one per
+ * sub-window), "host_prep_stream" (wall time begin to end, one entry per
+ * completed stream), "host_prep_stream_windows" (a count of sub-windows).
+ * pm_set_option("stream_upload_only", 1) (probes): the sub-windows go through
+ * the same staging but the two kernels are not launched; the hints are then
+ * meaningless. */
+int pm_batchpir_prep_stream_begin(pm_batchpir* h);
+int pm_batchpir_prep_stream_rows(pm_batchpir* h, uint32_t partition, uint32_t chunk0, uint32_t nchunks,
+                                 const uint64_t* rows, uint64_t nrows);
+int pm_batchpir_prep_stream_end(pm_batchpir* h);
+int pm_batchpir_prep_due(pm_batchpir* h);          /* 1 / 0; 0 for NULL */
+/* the server's side of the stream: rows of chunks [chunk0, chunk0+nchunks) of one partition */
+/* pm_batchpir_server_answer's sibling: copies, device to host, the rows
+ * pm_batchpir_prep_stream_rows takes for that range into rows and sets *nrows
+ * to their number (defined above; 0 for chunks past the end).  cap_rows < that
+ * number gives PM_EINVAL with *nrows set.  Reads the DB only: it works on a
+ * handle never preprocessed, on a client handle and on pm_graph_pir(g), and
+ * touches no client state.  PM_EINVAL: a NULL handle or nrows, "no DB on this
+ * handle", a partition out of range or not on this shard, nchunks 0, chunk0 +
+ * nchunks > SetSize. */
+int pm_batchpir_server_rows(pm_batchpir* h, uint32_t partition, uint32_t chunk0, uint32_t nchunks,
+                            uint64_t* rows, uint64_t cap_rows, uint64_t* nrows);
 /* The speculation record of this handle's last step (test hook), where the
  * fused step kernel (k_step, "host_path_step") ran it on a context created with
  * PM_STEP_SPEC=1: *nsub words in sub-query order (partition-major, qn slots per

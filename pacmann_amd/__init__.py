@@ -129,6 +129,12 @@ SIGNATURES = {
     "pm_batchpir_client_max_sets": (u64, [vp, u64]),
     "pm_batchpir_client_begin": (C.c_int, [vp, u64p, u64, u32p, u32p, u64, u64, u64p]),
     "pm_batchpir_client_finish": (C.c_int, [vp, u64p, u64, u64p, C.POINTER(C.c_uint8)]),
+    "pm_batchpir_create_remote": (C.c_int, [vp, u64, u64, u64, u64, u64, C.POINTER(vp)]),
+    "pm_batchpir_prep_stream_begin": (C.c_int, [vp]),
+    "pm_batchpir_prep_stream_rows": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u64]),
+    "pm_batchpir_prep_stream_end": (C.c_int, [vp]),
+    "pm_batchpir_prep_due": (C.c_int, [vp]),
+    "pm_batchpir_server_rows": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u64, u64p]),
     "pm_pir_export": (C.c_int, [vp, u32p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "pm_batchpir_export": (C.c_int, [vp, u64, u32p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "pm_graph_create": (C.c_int, [vp, u64, u64, u64, f32p, u32p, C.c_int, C.c_int, u64, u64, C.POINTER(vp)]),
@@ -574,6 +580,79 @@ class SimpleBatchPianoPIR:
         _check(lib().pm_batchpir_create_client(c.ctx.h, self.h, seed, C.byref(h)))
         c.h = h
         return c
+
+    @classmethod
+    def Remote(cls, DBSize: int, DBEntryByteNum: int, BatchSize: int, FailureProbLog2: int, seed: int = 1,
+               ctx: Context | None = None) -> "SimpleBatchPianoPIR":
+        """A client with no DB on the device (pm_batchpir_create_remote): keys, hints, counters and
+        localCache only.  Its hints come from PrepStreamBegin / PrepStreamRows / PrepStreamEnd (or
+        StreamPreprocessingFrom), its queries go through QueryBegin / QueryFinish; every call that would
+        read the DB raises "no DB on this handle"."""
+        c = cls.__new__(cls)
+        c.ctx = ctx or default_context()
+        c.E, c.shard, c.nshards, c._owned = DBEntryByteNum // 8, 0, 1, True
+        h = vp()
+        _check(lib().pm_batchpir_create_remote(c.ctx.h, DBSize, DBEntryByteNum, BatchSize, FailureProbLog2, seed,
+                                               C.byref(h)))
+        c.h = h
+        return c
+
+    def PrepStreamBegin(self):
+        """Open a streamed preprocessing (pm_batchpir_prep_stream_begin): Client.Initialization of every
+        partition with the next epoch's keys and zero hints.  Closes an open split query; on an open stream it
+        abandons that stream and starts over, which costs an epoch."""
+        _check(lib().pm_batchpir_prep_stream_begin(self.h))
+        _split_pending.pop(_handle_key(self.h), None)
+
+    def PrepStreamRows(self, partition: int, chunk0: int, nchunks: int, rows):
+        """UpdatePreprocessing of chunks [chunk0, chunk0 + nchunks) of one partition
+        (pm_batchpir_prep_stream_rows).  rows: [nrows, DBEntrySize] uint64, the existing rows of those chunks
+        (ServerRows of the same range); empty for chunks wholly past the partition's end."""
+        r = np.asarray(rows)
+        if r.dtype != np.uint64:
+            raise TypeError("rows must be uint64")
+        if r.size and (r.ndim != 2 or r.shape[1] != self.E):
+            raise ValueError("rows must be [nrows, DBEntrySize]")
+        r = np.ascontiguousarray(r)
+        n = r.shape[0] if r.size else 0
+        _check(lib().pm_batchpir_prep_stream_rows(self.h, partition, chunk0, nchunks, _p(r, u64p) if n else None, n))
+
+    def PrepStreamEnd(self):
+        """Close the stream once every chunk of every partition has come (pm_batchpir_prep_stream_end); the
+        handle then equals a Client twin of the same seed after as many Preprocessing calls."""
+        _check(lib().pm_batchpir_prep_stream_end(self.h))
+
+    @property
+    def prep_due(self) -> bool:
+        """pm_batchpir_prep_due: QueryFinish reached the re-preprocessing trigger on a handle with no DB; the
+        next QueryBegin waits for a streamed preprocessing."""
+        return bool(lib().pm_batchpir_prep_due(self.h))
+
+    def ServerRows(self, partition: int, chunk0: int, nchunks: int) -> np.ndarray:
+        """The server's side of the stream (pm_batchpir_server_rows): the existing rows of chunks [chunk0,
+        chunk0 + nchunks) of one partition, [nrows, DBEntrySize] uint64 (nrows 0 past the partition's end).
+        Reads the DB only."""
+        c = self._cfg(partition)
+        lo = chunk0 * c.ChunkSize
+        n = max(0, min((chunk0 + nchunks) * c.ChunkSize, c.DBSize) - lo)
+        out = np.zeros((n, self.E), dtype=np.uint64)
+        got = u64(0)
+        _check(lib().pm_batchpir_server_rows(self.h, partition, chunk0, nchunks, _p(out, u64p) if n else None, n,
+                                             C.byref(got)))
+        return out[:got.value]
+
+    def StreamPreprocessingFrom(self, server: "SimpleBatchPianoPIR", chunks_per_window: int | None = None):
+        """One whole streamed preprocessing of this handle from `server` (any handle over the same DB):
+        PrepStreamBegin, every partition's chunks in windows of chunks_per_window (None: a whole partition
+        per call) as ServerRows -> PrepStreamRows, PrepStreamEnd."""
+        self.PrepStreamBegin()
+        for p in range(self.Config()["PartitionNum"]):
+            ss = self._cfg(p).SetSize
+            step = ss if chunks_per_window is None else chunks_per_window
+            for c0 in range(0, ss, step):
+                nc = min(step, ss - c0)
+                self.PrepStreamRows(p, c0, nc, server.ServerRows(p, c0, nc))
+        self.PrepStreamEnd()
 
     def Preprocessing(self):
         _check(lib().pm_batchpir_preprocessing(self.h))

@@ -17,10 +17,10 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libpacmann.so"
 SOURCES = [CSRC / "pm_kernels.hip", CSRC / "pm_query.hip", CSRC / "pm_graph.hip", CSRC / "pm_graph_u8.hip",
-           CSRC / "pm_cluster.hip", CSRC / "pm_shard.hip",
+           CSRC / "pm_cluster.hip", CSRC / "pm_shard.hip", CSRC / "pm_stream.hip",
            CSRC / "pm_drl.hip", CSRC / "pm_knnb.hip", CSRC / "pm_ctx.cpp", CSRC / "pm_engine.cpp",
            CSRC / "pm_search.cpp", CSRC / "pm_group.cpp", CSRC / "pm_devloop.cpp",
-           CSRC / "pm_rccl.cpp", CSRC / "pm_build.cpp", CSRC / "pm_cluster.cpp"]
+           CSRC / "pm_rccl.cpp", CSRC / "pm_build.cpp", CSRC / "pm_cluster.cpp", CSRC / "pm_stream.cpp"]
 HEADERS = [CSRC / "pm_internal.h", CSRC / "pm_search_dev.h", CSRC / "pm_aes.h", CSRC / "pm_aes_bs.h",
            CSRC / "pm_host.h", CSRC / "pm_engine.h", CSRC / "pm_gvi_offs.h", CSRC / "pm_graph_dev.h", ROOT / "include" / "pacmann.h"]
 

@@ -147,6 +147,7 @@ extern "C" int pm_set_option(const char* name, int value) {
   if (!strcmp(name, "rccl_timeout_s")) { g_rccl_timeout_s.store(value); return 0; }
   if (!strcmp(name, "device_loop")) { g_device_loop.store(value < 0 ? -1 : value); return 0; }
   if (!strcmp(name, "fault_drl_query")) { g_fault_drl_query.store(value); return 0; }
+  if (!strcmp(name, "stream_upload_only")) { g_stream_upload_only.store(value > 0 ? 1 : 0); return 0; }
   if (!strcmp(name, "aes_bs")) { pmk::set_aes_bs(value); return 0; }
   if (!strcmp(name, "fold_rot")) {
     if (value < -1 || value > 1) return fail(PM_EINVAL, "fold_rot takes 1, 0 or -1");

@@ -53,10 +53,10 @@ namespace pmh {
 int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t B,
                          const uint64_t* rawDB, uint64_t F, uint64_t seed, bool batch,
                          uint32_t shard, uint32_t nshards, const Engine* server,
-                         const DbGen* gen, uint32_t coord_words) {
+                         const DbGen* gen, uint32_t coord_words, bool remote) {
   if (nshards == 0 || shard >= nshards) return fail(PM_EINVAL, "shard must be < nshards");
   if (!ctx) return fail(PM_EINVAL, "ctx is NULL");
-  if (!rawDB && N && !server && !gen) return fail(PM_EINVAL, "rawDB is NULL");
+  if (!rawDB && N && !server && !gen && !remote) return fail(PM_EINVAL, "rawDB is NULL");
   if (gen && gen->kind == 1 && (uint64_t)(gen->dim + gen->m) * 4 != Ebytes)
     return fail(PM_EINVAL, "graph entry size must be 4 * (dim + m)");
   if (server && server->ctx->device != ctx->device) return fail(PM_EINVAL, "a client shares the server DB of its own device only");
@@ -65,6 +65,7 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
   HIPCHK(hipSetDevice(ctx->device));
   g->ctx = ctx; g->is_batch = batch;
   g->N = N; g->Ebytes = Ebytes; g->E = Ebytes / 8; g->F = F; g->seed = seed;
+  g->remote = remote;
   if (batch) {
     g->B = B;
     g->P = B / 2;   // BatchSize / RealQueryPerPartition (batch-pir.go:62)
@@ -119,8 +120,8 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
   CHK(g->zero16.reserve(64));
   HIPCHK(hipMemset(g->zero16.p, 0, 64));
   if (server) g->db = server->db;   // same N, entry size, partitions and shard: same packed rows
-  else CHK(g->db->reserve(std::max<uint64_t>(8, off_db * g->E * 8)));
-  for (uint32_t i : server ? std::vector<uint32_t>{} : g->owned_list) {
+  else if (!remote) CHK(g->db->reserve(std::max<uint64_t>(8, off_db * g->E * 8)));   // a remote client holds no rows
+  for (uint32_t i : server || remote ? std::vector<uint32_t>{} : g->owned_list) {
     const uint64_t start = (uint64_t)i * g->PS, rows = g->parts[i].d.N;
     uint64_t* dst = g->db->as<uint64_t>() + g->parts[i].d.row0 * g->E;
     if (gen && gen->kind == 0)
@@ -149,9 +150,9 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
   // The same property lets the pair answer gather packed rows (the row image
   // below), so the reduction runs once if either image wants it.
   uint64_t off_img = 0;
-  const bool fold_img = !g->owned_list.empty() && pmk::fold_image_ok(g->minCS, g->maxCS, (uint32_t)g->E);
+  const bool fold_img = !remote && !g->owned_list.empty() && pmk::fold_image_ok(g->minCS, g->maxCS, (uint32_t)g->E);
   const uint32_t want_npk = !server && fold_img ? pmk::fold_pack_slices(g->minCS, g->maxCS, (uint32_t)g->E, coord_words) : 0;
-  const uint32_t want_apk = !server && !g->owned_list.empty() ? pmk::answer_pack_segs((uint32_t)g->E, coord_words) : 0;
+  const uint32_t want_apk = !server && !remote && !g->owned_list.empty() ? pmk::answer_pack_segs((uint32_t)g->E, coord_words) : 0;
   bool low_zero = false;
   if (want_npk || want_apk) {
     DevBuf flag;
@@ -218,7 +219,8 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
   CHK(g->arena.reserve(std::max<uint64_t>(8, off_ar * 8)));
   // the chunk-major PRF table only where the fold reads it (every other reader uses tabT):
   // SIFT1M's rotated fold and the BIGANN wide fold do not, saving H*SS*2 B per partition
-  const bool need_tab = pmk::fold_needs_tab(g->minCS, g->maxCS, (uint32_t)g->E, off_img != 0);
+  // (nor for a remote client: the streamed fold reads tabT)
+  const bool need_tab = !remote && pmk::fold_needs_tab(g->minCS, g->maxCS, (uint32_t)g->E, off_img != 0);
   if (need_tab) CHK(g->tab.reserve(off_tab * 2));
   CHK(g->tabT.reserve(off_tabT * 2));
   CHK(g->cur.reserve(std::max<uint64_t>(2, off_cur * 2)));
@@ -1088,6 +1090,7 @@ extern "C" int pm_batchpir_create_synth(pm_ctx* ctx, uint64_t DBSize, uint64_t D
 }
 extern "C" int pm_batchpir_create_client(pm_ctx* ctx, pm_batchpir* server, uint64_t seed, pm_batchpir** out) {
   if (!out || !server) return fail(PM_EINVAL, "NULL argument");
+  CHK(db_guard(&server->e));
   const Engine& s = server->e;
   pm_batchpir* h = new pm_batchpir();
   int r = engine_create(ctx, &h->e, s.N, s.Ebytes, s.B, nullptr, s.F, seed, true, s.shard, s.nshards, &s);
@@ -1096,12 +1099,34 @@ extern "C" int pm_batchpir_create_client(pm_ctx* ctx, pm_batchpir* server, uint6
   *out = h;
   return 0;
 }
+// A client with no DB on the device: engine_create's parameters, keys and hint tables,
+// filled by streamed preprocessings (pm_stream.cpp).
+extern "C" int pm_batchpir_create_remote(pm_ctx* ctx, uint64_t DBSize, uint64_t DBEntryByteNum, uint64_t BatchSize,
+                                         uint64_t F, uint64_t seed, pm_batchpir** out) {
+  if (!out) return fail(PM_EINVAL, "out is NULL");
+  if (!ctx) return fail(PM_EINVAL, "ctx is NULL");
+  if (DBSize == 0) return fail(PM_EINVAL, "DBSize must be > 0");
+  if (DBEntryByteNum < 8) return fail(PM_EINVAL, "DBEntryByteNum must be >= 8");
+  if (BatchSize < 2) return fail(PM_EINVAL, "BatchSize must be >= 2");
+  pm_batchpir* h = new pm_batchpir();
+  int r = engine_create(ctx, &h->e, DBSize, DBEntryByteNum, BatchSize, nullptr, F, seed, true, 0, 1, nullptr, nullptr, 0,
+                        true);
+  if (r) { delete h; return r; }
+  *out = h;
+  return 0;
+}
 extern "C" void pm_batchpir_destroy(pm_batchpir* h) { delete h; }
 namespace pmh {
-int split_guard(const Engine* g) {
+int client_guard(const Engine* g) {
+  if (g->pstream.open) return fail(PM_EINVAL, "a streamed preprocessing is open");
   return g->split.open ? fail(PM_EINVAL, "a split query is open") : 0;
 }
+int db_guard(const Engine* g) {
+  return g->remote ? fail(PM_EINVAL, "no DB on this handle") : 0;
+}
 int batch_prep(Engine* g) {   // Preprocessing (batch-pir.go:119-155)
+  CHK(db_guard(g));
+  g->pstream.open = false;   // ... and an open stream has nothing left to fill
   g->split.open = false;   // every hint is rebuilt: an open split query (pm_batchpir_client_begin) has nothing left to finish
   g->FBN = 0; g->QMIP = 0;
   auto t0 = std::chrono::steady_clock::now();
@@ -1114,9 +1139,10 @@ int batch_prep(Engine* g) {   // Preprocessing (batch-pir.go:119-155)
 }  // namespace pmh
 extern "C" int pm_batchpir_preprocessing(pm_batchpir* h) { return batch_prep(&h->e); }
 extern "C" int pm_batchpir_dummy_preprocessing(pm_batchpir* h) {   // batch-pir.go:157-166
-  CHK(split_guard(&h->e));
+  CHK(client_guard(&h->e));
   h->e.skipPrep = true;
-  CHK(engine_prep(&h->e, 0, h->e.P));
+  CHK(engine_prep(&h->e, 0, h->e.P));   // (reads no DB: zero hints)
+  h->e.prepared = true;
   record_stats(&h->e, 0);
   return 0;
 }
@@ -1134,7 +1160,8 @@ namespace pmh {
 int batch_query(Engine* g, const uint64_t* idx, uint64_t n, uint64_t* out, const float* q_dev,
                        uint32_t dim, float* dist_out, const uint64_t** rows_out,
                        uint8_t* ok) {
-  CHK(split_guard(g));
+  CHK(db_guard(g));
+  CHK(client_guard(g));
   auto t = Clock::now();
   int r = batch_query_impl(g, idx, n, out, q_dev, dim, dist_out, rows_out, ok);
   g->ctx->host_add(HT_BATCH_QUERY, ms_since(t));
@@ -1156,7 +1183,7 @@ namespace pmh {
 //   bq_tail      FinishedBatchNum / QueriesMadeInPartition and the
 //                re-preprocessing trigger (:238-247).
 int bq_prepare(Engine* g, const uint64_t* idx, uint64_t n, bool* fast) {
-  CHK(split_guard(g));   // (the entry points check first, before they change anything)
+  CHK(client_guard(g));   // (the entry points check first, before they change anything)
   const uint64_t E = g->E, P = g->P;
   CHK(ensure_host_cache(g));
   if (g->zero_row.size() != E) g->zero_row.assign(E, 0);
@@ -1218,7 +1245,8 @@ void bq_emit_fast(Engine* g, const uint64_t* idx, uint64_t n, uint64_t* out, flo
 }
 int bq_tail(Engine* g, uint64_t n) {
   if (g->QMIP >= g->parts[0].maxq64 - 2) {
-    CHK(batch_prep(g));
+    if (g->remote) g->prep_due = true;   // no DB to preprocess over: the caller streams it (pm_batchpir_prep_due)
+    else CHK(batch_prep(g));
   } else {
     g->FBN += n / g->B;
     g->QMIP += g->qn;
@@ -1309,7 +1337,8 @@ extern "C" int pm_batchpir_query_dev(pm_batchpir* h, const uint64_t* ids, uint64
                                      void* stream) {
   Engine* g = &h->e;
   if (n && (!ids || !dev_out)) return fail(PM_EINVAL, "NULL argument");
-  CHK(split_guard(g));
+  CHK(db_guard(g));
+  CHK(client_guard(g));
   auto t = Clock::now();
   const int r = query_dev_impl(g, ids, n, dev_out, (hipStream_t)stream);
   g->ctx->host_add(HT_BATCH_QUERY, ms_since(t));
@@ -1421,6 +1450,7 @@ extern "C" int pm_batchpir_server_answer(pm_batchpir* h, const uint32_t* parts, 
   Engine* g = &h->e;
   pm_ctx* c = g->ctx;
   const uint64_t E = g->E;
+  CHK(db_guard(g));
   if (stride < pm_batchpir_max_set_size(h)) return fail(PM_EINVAL, "stride must be >= the largest SetSize");
   if (stride >> 32) return fail(PM_EINVAL, "stride must be < 2^32");
   // every set is checked before any HIP call; the rows each chunk gathers are counted on the way
@@ -1485,7 +1515,9 @@ extern "C" int pm_batchpir_client_begin(pm_batchpir* h, const uint64_t* ids, uin
   Engine* g = &h->e;
   pm_ctx* c = g->ctx;
   const uint64_t E = g->E, P = g->P, qn = n / P;
-  CHK(split_guard(g));
+  CHK(client_guard(g));
+  if (g->remote && !g->prepared) return fail(PM_EINVAL, "not preprocessed");
+  if (g->prep_due) return fail(PM_EINVAL, "preprocessing due: stream it first");
   if (g->nshards > 1) return fail(PM_EINVAL, "the client role is not built for shard handles");
   if (E > pmk::client_max_e() || g->maxSS > pmk::client_max_ss())
     return fail(PM_EINVAL, "the client role serves DBEntrySize <= 256 words and SetSize <= 1024");
@@ -1563,6 +1595,7 @@ extern "C" int pm_batchpir_client_finish(pm_batchpir* h, const uint64_t* answers
   Engine* g = &h->e;
   pm_ctx* c = g->ctx;
   Engine::SplitQuery& Q = g->split;
+  if (g->pstream.open) return fail(PM_EINVAL, "a streamed preprocessing is open");
   if (!Q.open) return fail(PM_EINVAL, "no split query is open");
   if (nq != Q.nq) return fail(PM_EINVAL, "nq is not the number of sets pm_batchpir_client_begin returned");
   auto t_begin = Clock::now();

@@ -24,7 +24,7 @@ namespace pmh {
 int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t B,
                   const uint64_t* rawDB, uint64_t F, uint64_t seed, bool batch,
                   uint32_t shard = 0, uint32_t nshards = 1, const Engine* server = nullptr,
-                  const DbGen* gen = nullptr, uint32_t coord_words = 0);
+                  const DbGen* gen = nullptr, uint32_t coord_words = 0, bool remote = false);
 int ensure_host_cache(Engine* g);
 int engine_prep_host(Engine* g, uint64_t p0, uint64_t p1, std::vector<uint64_t>& todo,
                      hipStream_t st = nullptr);
@@ -40,7 +40,10 @@ constexpr int kChainStop = 1 << 30;   // after_resolve's return value that ends 
 int step_chain(pm_ctx* c, StepBufs& B, PmStep& S, const pmk::StepShape& shape, uint32_t nreal, double ans_bytes,
                const std::function<int()>& after_resolve = {});
 int engine_step(Engine* g, const float* q_dev, uint32_t dim);
-int split_guard(const Engine* g);   // PM_EINVAL "a split query is open" while the engine has one
+// PM_EINVAL while the engine has an open split query ("a split query is open") or an open streamed
+// preprocessing ("a streamed preprocessing is open"): the first check of every client call
+int client_guard(const Engine* g);
+int db_guard(const Engine* g);   // PM_EINVAL "no DB on this handle" for a remote engine (pm_batchpir_create_remote)
 void print_stamps(const Engine& e);
 void record_stats(Engine* g, double t);
 int batch_prep(Engine* g);
@@ -259,6 +262,25 @@ struct Engine {
     DevBuf sets_d, ans_d, map_d;   // [nsub][qw] sets then [nsub] modes; [nq][E] answers; [nsub] map
     HostBuf sets_h;                // the sets and modes, down
   } split;
+  // A client with no DB on the device (pm_batchpir_create_remote): db, img, apk and tab stay
+  // empty, and its hints come from streamed preprocessings alone.  prepared: a stream has completed (or
+  // DummyPreprocessing ran); prep_due: the re-preprocessing trigger fired in pm_batchpir_client_finish, which
+  // cannot preprocess here, and the next begin waits for a stream.
+  bool remote = false, prepared = false, prep_due = false;
+  // The streamed preprocessing (pm_stream.cpp): which chunks have come, and two pinned staging slots with
+  // their device windows, reused round-robin (ev[i]: slot i's last upload and kernels).
+  struct PrepStream {
+    bool open = false;
+    std::vector<std::vector<char>> got;   // [P][SS] chunk delivered
+    uint64_t missing = 0;                 // chunks still to come
+    HostBuf stage[2];
+    DevBuf win[2];
+    hipEvent_t ev[2] = {};
+    bool busy[2] = {};                    // ev[i] has been recorded
+    uint64_t slot_bytes = 0;
+    uint32_t next = 0;
+    std::chrono::steady_clock::time_point t0;
+  } pstream;
   StepBufs buf;   // the step's scratch (engine_step)
   std::vector<double> stamp_sum;   // PM_STAMPS builds: accumulated phase deltas
   uint64_t stamp_n = 0;
@@ -273,6 +295,7 @@ struct Engine {
     if (dev_ev) (void)hipEventDestroy(dev_ev);
     if (stage_ev) (void)hipEventDestroy(stage_ev);
     if (order_ev) (void)hipEventDestroy(order_ev);
+    for (hipEvent_t e : pstream.ev) if (e) (void)hipEventDestroy(e);
   }
   std::vector<PartHost> parts;
   uint32_t maxH = 0, maxPH = 0, maxSS = 0, maxRepl = 0, maxCS = 0, minCS = ~0u;

@@ -906,6 +906,7 @@ extern "C" int pm_batchpir_group_create(pm_batchpir** clients, uint32_t S, pm_ba
   if (!clients || !S || !out) return fail(PM_EINVAL, "NULL argument");
   for (uint32_t i = 0; i < S; ++i) {
     if (!clients[i]) return fail(PM_EINVAL, "NULL client");
+    CHK(db_guard(&clients[i]->e));
     const Engine& a = clients[0]->e;
     const Engine& b = clients[i]->e;
     if (a.db.get() != b.db.get() || a.P != b.P || a.E != b.E || a.N != b.N || a.shard != b.shard ||
@@ -928,7 +929,7 @@ extern "C" int pm_batchpir_group_create(pm_batchpir** clients, uint32_t S, pm_ba
 extern "C" void pm_batchpir_group_destroy(pm_batchpir_group* h) { delete h; }
 extern "C" int pm_batchpir_group_preprocessing(pm_batchpir_group* h) {
   if (!h) return fail(PM_EINVAL, "NULL argument");
-  for (Engine* e : h->G.es) CHK(split_guard(e));
+  for (Engine* e : h->G.es) CHK(client_guard(e));
   // SimpleBatchPianoPIR.Preprocessing (batch-pir.go:119-155) of every client,
   // as ONE launch set: each partition's K clients fold side by side
   return group_prep(h->G, std::vector<char>(h->G.S, 1), nullptr);
@@ -938,7 +939,7 @@ extern "C" int pm_batchpir_group_query(pm_batchpir_group* h, const uint64_t* ids
   if (!h || (!ids && n) || (!out && n)) return fail(PM_EINVAL, "NULL argument");
   StepGroup& G = h->G;
   const uint64_t E = G.E;
-  for (uint32_t s = 0; s < G.S; ++s) CHK(split_guard(G.es[s]));   // before any client's state moves
+  for (uint32_t s = 0; s < G.S; ++s) CHK(client_guard(G.es[s]));   // before any client's state moves
   for (uint32_t s = 0; s < G.S; ++s) {   // bucketing; clients at a partition's budget go alone
     Engine* e = G.es[s];
     bool f = false;

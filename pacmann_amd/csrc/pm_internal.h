@@ -386,6 +386,15 @@ int prep_fold(hipStream_t st, const PmPart* dparts, int nparts, uint32_t maxH, c
               bool have_img = false, uint32_t minH = 0, uint32_t npk = 0);
 void prep_repl(hipStream_t st, const PmPart* dparts, int nparts, uint32_t maxRepl,
                const uint64_t* db, uint32_t E);
+// The streamed preprocessing (pm_stream.hip; pm_batchpir_prep_stream_rows): UpdatePreprocessing of chunks
+// [c0, c0 + nc) of partition parts[part] from `win`, the nrows existing rows of those chunks (row i of win =
+// partition row c0 * CS + i; nothing at or past nrows is read).  stream_fold XORs the window's selected rows
+// into the parities (read-modify-write; nothing is launched for E < 4 or an empty window); stream_repl
+// writes the window's replacement indices and values.  H, Qpc: the partition's.
+void stream_fold(hipStream_t st, const PmPart* parts, uint32_t part, uint32_t H, const uint64_t* win, uint32_t c0,
+                 uint32_t nc, uint32_t nrows, uint32_t E);
+void stream_repl(hipStream_t st, const PmPart* parts, uint32_t part, uint32_t Qpc, const uint64_t* win, uint32_t c0,
+                 uint32_t nc, uint32_t nrows, uint32_t E);
 // The bank-rotated fold's DB image (CS 512 / 1,024, even E, E >= 4): whether an
 // engine being created should have one (the shape fits and "fold_rot" /
 // PM_FOLD_ROT allows it; not to be asked at launch time, see fold_form), its

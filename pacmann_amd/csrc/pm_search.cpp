@@ -10,7 +10,7 @@
 namespace pmh {
 int check_session(const pm_graph* g) {
   if (!g->lost.empty()) return fail(PM_EINVAL, "session state lost: " + g->lost);
-  if (g->pir) CHK(split_guard(&g->pir->e));
+  if (g->pir) CHK(client_guard(&g->pir->e));
   return 0;
 }
 }  // namespace pmh
