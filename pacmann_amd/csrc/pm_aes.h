@@ -68,11 +68,23 @@ __device__ __forceinline__ uint32_t aes_x3(uint32_t a, uint32_t b, uint32_t c) {
   return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 }
 
-// Fill the replicated table.  Call with the whole block, then __syncthreads().
+// Fill the replicated table.  Call with the whole block of NT threads, then
+// __syncthreads().  Word i holds entry (i >> 6) & 255, rotated in the Te2 half
+// (i & 32); with NT a multiple of 64 a thread's words tid + NT k all lie in the
+// same half and NT / 64 entries apart, so a word costs one load, one
+// v_alignbit_b32 and one ds_write at immediate offsets (the loop over i with
+// its shifts, masks and selects cost 9 VALU per word: 18 per PRF of
+// k_prep_offsets, whose threads fill 16 words for 8 PRFs).
+template <int NT>
 __device__ __forceinline__ void aes_lds_init(uint32_t* te, const uint32_t* __restrict__ g_te0) {
-  for (int i = threadIdx.x; i < kTeLdsWords; i += blockDim.x) {
-    const uint32_t t = g_te0[(i >> 6) & 255];
-    te[i] = (i & 32) ? rotl32(t, 16) : t;   // Te0 | Te2
+  static_assert(NT % 64 == 0 && kTeLdsWords % NT == 0, "whole 64-word entry rows per pass");
+  const uint32_t rot = (threadIdx.x & 32u) ? 16u : 0u;   // Te0 | Te2 = rotl16(Te0)
+  const uint32_t* src = g_te0 + (threadIdx.x >> 6);
+  uint32_t* dst = te + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kTeLdsWords / NT; ++k) {
+    const uint32_t t = src[NT / 64 * k];
+    dst[NT * k] = __builtin_amdgcn_alignbit(t, t, rot);
   }
 }
 
@@ -171,14 +183,32 @@ __device__ __forceinline__ uint32_t prf_lo32_split(const AesLane& A, const uint3
 // The low 16 bits of the same PRF (the hint tables keep PRF & (ChunkSize - 1),
 // ChunkSize <= 2^15).  Output bytes 0 and 1 of the last round are S[s0 byte 0]
 // and S[s1 byte 1], so round 9 computes only columns 0 and 1 and round 10 two
-// S-box bytes: 122 lookups per PRF instead of 132.
-__device__ __forceinline__ uint32_t prf_lo16_split(const AesLane& A, const uint32_t* __restrict__ rk,
-                                                   const R1Uniform& u, const R1Lane& v, uint32_t x) {
-  uint32_t s0 = u.u0 ^ v.v0, s1 = u.u1 ^ v.v1, s2 = u.u2 ^ v.v2, s3 = u.u3 ^ v.v3;
-  aes_rounds<2, 9>(A, rk, s0, s1, s2, s3);
+// S-box bytes: 122 lookups per PRF instead of 132.  The two lookups come back
+// as whole table words (Te0 = {2S, S, S, 3S}: the S-box byte is byte 1 of
+// each), so that the caller takes both bytes out with ONE v_perm_b32 and puts
+// two chunks' values into one word with two (lo16_pair): the kernel is
+// VALU-bound, and shift / mask / or per value cost three more per PRF.
+struct Lo16Words { uint32_t w0, w1; };
+__device__ __forceinline__ Lo16Words lo16_tail(const AesLane& A, const uint32_t* __restrict__ rk, uint32_t s0,
+                                               uint32_t s1, uint32_t s2, uint32_t s3) {
   const uint32_t t0 = A.col(s0, s1, s2, s3, rk[36]);
   const uint32_t t1 = A.col(s1, s2, s3, s0, rk[37]);
-  return ((A.Sk<0>(t0) | (A.Sk<1>(t1) << 8)) ^ rk[40] ^ x) & 0xffffu;
+  return Lo16Words{A.Tk<0>(t0), A.Tk<1>(t1)};
+}
+// The cipher's low 16 bits of two blocks in one word, a's low and b's high,
+// XORed with x2: two v_perm_b32 and one v_bitop3_b32 ((A | B) ^ x2).  PRF =
+// cipher ^ rk[40] ^ x, and rk[40] ^ x is the same for every tag: x2 is the
+// caller's scalar for the two chunks.  Bits 8-15 and 24-31 of the table words
+// do not come through, so the caller masks after, not before.
+__device__ __forceinline__ uint32_t lo16_pair(const Lo16Words& a, const Lo16Words& b, uint32_t x2) {
+  return __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_perm(a.w1, a.w0, 0x0c0c0501u),
+                                     __builtin_amdgcn_perm(b.w1, b.w0, 0x05010c0cu), x2, 0x56);
+}
+__device__ __forceinline__ Lo16Words prf_lo16_split(const AesLane& A, const uint32_t* __restrict__ rk,
+                                                    const R1Uniform& u, const R1Lane& v) {
+  uint32_t s0 = u.u0 ^ v.v0, s1 = u.u1 ^ v.v1, s2 = u.u2 ^ v.v2, s3 = u.u3 ^ v.v3;
+  aes_rounds<2, 9>(A, rk, s0, s1, s2, s3);
+  return lo16_tail(A, rk, s0, s1, s2, s3);
 }
 // Chunks x < 256 (SetSize <= 256: SIFT1M's 124, MS-MARCO's 196): after the
 // whitening only byte 0 of s0 depends on x, so of round 1's output only column
@@ -198,15 +228,13 @@ __device__ __forceinline__ R2Hint r2_hint(const AesLane& A, const uint32_t* __re
                 A.Tk<0>(s2) ^ rk[10] ^ rotl32(A.Tk<1>(s3) ^ A.T2k<3>(s1), 8),
                 A.Tk<0>(s3) ^ A.T2k<2>(s1) ^ rk[11] ^ rotl32(A.T2k<3>(s2), 8)};
 }
-// = prf_lo16_split(A, rk, u, v, x) for x < 256, given u0 = r1_uniform(x).u0 and r2_hint.
-__device__ __forceinline__ uint32_t prf_lo16_r2(const AesLane& A, const uint32_t* __restrict__ rk, uint32_t u0,
-                                                const R1Lane& v, const R2Hint& k, uint32_t x) {
+// = prf_lo16_split(A, rk, u, v) for x < 256, given u0 = r1_uniform(x).u0 and r2_hint.
+__device__ __forceinline__ Lo16Words prf_lo16_r2(const AesLane& A, const uint32_t* __restrict__ rk, uint32_t u0,
+                                                 const R1Lane& v, const R2Hint& k) {
   const uint32_t s = u0 ^ v.v0;
   uint32_t s0 = A.Tk<0>(s) ^ k.k0, s1 = rotl32(A.T2k<3>(s), 8) ^ k.k1;
   uint32_t s2 = A.T2k<2>(s) ^ k.k2, s3 = rotl32(A.Tk<1>(s), 8) ^ k.k3;
   aes_rounds<3, 9>(A, rk, s0, s1, s2, s3);
-  const uint32_t t0 = A.col(s0, s1, s2, s3, rk[36]);
-  const uint32_t t1 = A.col(s1, s2, s3, s0, rk[37]);
-  return ((A.Sk<0>(t0) | (A.Sk<1>(t1) << 8)) ^ rk[40] ^ x) & 0xffffu;
+  return lo16_tail(A, rk, s0, s1, s2, s3);
 }
 }  // namespace pm

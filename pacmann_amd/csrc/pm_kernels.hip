@@ -36,7 +36,8 @@ constexpr int kOffsBlock = 1024;   // 64 KiB of replicated table per workgroup: 
 
 // Initial PRF tables of every hint h < H (its tag is h) at 8 chunks per
 // workgroup, written chunk-major (hint search) and hint-major (set
-// expansion).  Bound by the AES T-table lookups in LDS: the hint-major stores
+// expansion).  Bound by the AES: its VALU issue (238 per PRF) and its T-table
+// lookups in LDS (114) are both 0.83-0.87 busy.  The hint-major stores
 // are scattered 2-B writes (every lane on its own line, ~5x their bytes in
 // HBM write traffic), yet staging them through LDS made the kernel 20-25 %
 // slower (375 -> 450-470 us at SIFT1M shape), so they stay direct (without
@@ -47,56 +48,124 @@ constexpr int kOffsBlock = 1024;   // 64 KiB of replicated table per workgroup: 
 #define PM_OFFS_TILES 1   // 8-chunk tiles per workgroup sharing one 64 KiB table fill (2 and 4 measured no faster: 244 / 268 vs 240 us per client alone)
 #endif
 constexpr int kOffsTiles = PM_OFFS_TILES;
-__global__ void __launch_bounds__(kOffsBlock, 1) k_prep_offsets(const PmPart* __restrict__ parts) {
-  __shared__ uint32_t te[kTeLdsWords];
-  __shared__ R1Uniform r1u[kOffsTiles][kOffsChunksPerBlock];
-  const PmPart& P = parts[blockIdx.z];
-  const uint32_t H = P.H, SS = P.SS;
-  const uint32_t cb = blockIdx.y * kOffsChunksPerBlock * kOffsTiles;
-  if (blockIdx.x * kOffsBlock >= H || cb >= SS) return;   // block-uniform
-  aes_lds_init(te, g_aes.te0);
-  __syncthreads();
-  const AesLane A(te, threadIdx.x);
-  const uint32_t cend = min(SS, cb + kOffsChunksPerBlock * kOffsTiles);
-  // round 1's chunk-dependent half, once per chunk for the workgroup (pm_aes.h)
-  if (threadIdx.x < cend - cb)
-    r1u[threadIdx.x / kOffsChunksPerBlock][threadIdx.x % kOffsChunksPerBlock] = r1_uniform(A, P.rk, cb + threadIdx.x);
-  __syncthreads();
-  const uint32_t h = blockIdx.x * kOffsBlock + threadIdx.x;
-  if (h >= H) return;
-  const uint32_t mask = P.CS - 1;
-  const uint32_t own = h >= P.PH ? (h - P.PH) / P.Qpc : 0xffffffffu;
-  uint16_t* o = P.tab;
+
+// a 2-B store at a wave-uniform row plus a lane's fixed 32-bit byte offset: the
+// row is scalar arithmetic, the store's address one 64-bit VALU add
+__device__ __forceinline__ void store16_row(PM_G uint16_t* row, uint32_t lane_bytes, uint32_t v) {
+  *reinterpret_cast<PM_G uint16_t*>(reinterpret_cast<PM_G char*>(row) + lane_bytes) = (uint16_t)v;
+}
+
+// The tiles of one workgroup.  The kernel is bound by VALU issue (DESIGN.md
+// §5.6), so everything that is not AES is decided outside the chunk loop: the
+// AES form (R2: SetSize <= 256, pm_aes.h r2_hint) and the chunk-major table
+// (TAB: only where the fold reads it) are template parameters, a lane's
+// offsets into a cur row and a tab row are computed once and the rows advance
+// in SGPRs, two chunks share one pack / mask / key step and one register (its
+// halves are stored with global_store_short and _d16_hi), and a backup hint's
+// own chunk is patched after the tile instead of being compared against every
+// chunk.  SetSize is a multiple of 4 (part_params): a pair of chunks is whole.
+template <bool R2, bool TAB>
+__device__ __forceinline__ void prep_offsets_tiles(const PmPart& P, const AesLane& A,
+                                                   const R1Uniform (&r1u)[kOffsTiles][kOffsChunksPerBlock],
+                                                   const uint32_t (&r1u0)[kOffsTiles][kOffsChunksPerBlock],
+                                                   uint32_t cb, uint32_t h) {
+  const uint32_t H = P.H, SS = P.SS, PH = P.PH, K = P.curk;
+  const uint32_t m = P.CS - 1, m2 = m | (m << 16);
+  const uint32_t k2 = (P.rk[40] & 0xffffu) * 0x10001u;   // rk[40]'s low half in both halves
+  const bool prim = h < PH;
+  const uint32_t own = prim ? 0xffffffffu : (h - PH) / P.Qpc;
+  const uint32_t lcur = cur_row_off(K, h) * 2, ltab = h * 2;   // bytes; H < 2^29 (engine_create)
+  const uint64_t cur_group = (uint64_t)cur_blocks(PH) * K * 8;   // cur words per K chunks (cur_index)
   const R1Lane r1v = r1_lane(A, P.rk, h);   // initial tag of hint h is h
-  // SetSize <= 256: round 2's hint-only part once per hint (pm_aes.h r2_hint)
-  const bool r2 = SS <= 256;
-  const R2Hint r2k = r2 ? r2_hint(A, P.rk, r1u[0][0], r1v) : R2Hint{0, 0, 0, 0};
-  static_assert(kOffsChunksPerBlock == 8, "one 16-B tabT tile of 8 chunks per thread");
+  R2Hint r2k{0, 0, 0, 0};
+  if (R2) r2k = r2_hint(A, P.rk, r1u[0][0], r1v);
   for (int tl = 0; tl < kOffsTiles; ++tl) {
     const uint32_t c0 = cb + tl * kOffsChunksPerBlock;
     if (c0 >= SS) break;
     const uint32_t c1 = min(SS, c0 + kOffsChunksPerBlock);
-    uint16_t tile[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) tile[j] = kSkip;   // chunks past SetSize: padding
-    auto put = [&](uint32_t c, uint32_t prf) {
-      uint16_t v = (uint16_t)(prf & mask);
-      v = (c == own) ? kSkip : v;
-      if (o) o[(uint64_t)c * H + h] = v;   // chunk-major (only the folds that stage it read it)
-      tile[c - c0] = v;
-      if (h < P.PH) P.cur[cur_index(P.PH, P.curk, c, h)] = v;   // hint search (tags start at h)
+    // chunk c0's cur row as (group, chunk in group); next_cur steps it without a division
+    const uint32_t cq = K == 2 ? c0 >> 1 : K == 1 ? c0 : c0 / K;
+    uint32_t cr = c0 - cq * K;
+    uint64_t crow = cq * cur_group + cr * 8;
+    auto next_cur = [&] {
+      if (++cr == K) { cr = 0; crow += cur_group - (K - 1) * 8; }
+      else crow += 8;
     };
-    for (uint32_t c = c0; c < c1; ++c)
-      put(c, r2 ? prf_lo16_r2(A, P.rk, r1u[tl][c - c0].u0, r1v, r2k, c) : prf_lo16_split(A, P.rk, r1u[tl][c - c0], r1v, c));
-    uint4 t4;   // tag-major tile (set expansion): one 16-B store
-    t4.x = tile[0] | ((uint32_t)tile[1] << 16); t4.y = tile[2] | ((uint32_t)tile[3] << 16);
-    t4.z = tile[4] | ((uint32_t)tile[5] << 16); t4.w = tile[6] | ((uint32_t)tile[7] << 16);
+    uint64_t trow = (uint64_t)c0 * H;   // chunk c0's tab row
+    uint32_t w[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};   // chunks past SetSize: kSkip padding
+    uint32_t u0[kOffsChunksPerBlock];   // R2: the tile's round-1 words, two 16-B LDS reads
+#pragma unroll
+    for (int i = 0; i < kOffsChunksPerBlock; ++i) u0[i] = R2 ? r1u0[tl][i] : 0u;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {   // chunks c, c + 1: word p of the tile
+      const uint32_t c = c0 + 2 * p;
+      if (c >= c1) break;   // block-uniform, like everything about c below
+      const Lo16Words a = R2 ? prf_lo16_r2(A, P.rk, u0[2 * p], r1v, r2k) : prf_lo16_split(A, P.rk, r1u[tl][2 * p], r1v);
+      const Lo16Words b = R2 ? prf_lo16_r2(A, P.rk, u0[2 * p + 1], r1v, r2k) : prf_lo16_split(A, P.rk, r1u[tl][2 * p + 1], r1v);
+      const uint32_t kx = k2 ^ (c | ((c + 1) << 16));   // rk[40] ^ x of both chunks: a scalar
+      const uint32_t v = lo16_pair(a, b, kx) & m2;
+      w[p] = v;
+      if (TAB) {   // chunk-major (only the folds that stage it read it)
+        store16_row(P.tab + trow, ltab, v);
+        store16_row(P.tab + trow + H, ltab, v >> 16);
+        trow += 2 * (uint64_t)H;
+      }
+      const uint64_t crow_a = crow;
+      next_cur();
+      const uint64_t crow_b = crow;
+      next_cur();
+      if (prim) {   // hint search (tags start at h)
+        store16_row(P.cur + crow_a, lcur, v);
+        store16_row(P.cur + crow_b, lcur, v >> 16);
+      }
+    }
+    // a backup hint's own chunk (pir.go:332-334), if it is one of this tile's: kSkip
+    const uint32_t j = own - c0;
+    if (j < c1 - c0) {
+      const uint32_t half = (j & 1) ? 0xffff0000u : 0x0000ffffu;
+#pragma unroll
+      for (uint32_t p = 0; p < 4; ++p) w[p] |= (j >> 1) == p ? half : 0u;
+      if (TAB) P.tab[(uint64_t)own * H + h] = kSkip;   // after this lane's store of the PRF value above
+    }
+    // tag-major tile (set expansion): one 16-B store
     if (PM_PREP_NT) {
       typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-      __builtin_nontemporal_store(u32x4{t4.x, t4.y, t4.z, t4.w}, reinterpret_cast<u32x4*>(P.tabT + tabT_index(H, h, c0)));
+      __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4*>(P.tabT + tabT_index(H, h, c0)));
     } else {
-      *reinterpret_cast<uint4*>(P.tabT + tabT_index(H, h, c0)) = t4;
+      *reinterpret_cast<uint4*>(P.tabT + tabT_index(H, h, c0)) = make_uint4(w[0], w[1], w[2], w[3]);
     }
+  }
+}
+
+__global__ void __launch_bounds__(kOffsBlock, 1) k_prep_offsets(const PmPart* __restrict__ parts) {
+  __shared__ uint32_t te[kTeLdsWords];
+  __shared__ R1Uniform r1u[kOffsTiles][kOffsChunksPerBlock];
+  __shared__ __attribute__((aligned(16))) uint32_t r1u0[kOffsTiles][kOffsChunksPerBlock];   // their u0 words, side by side
+  const PmPart& P = parts[blockIdx.z];
+  const uint32_t H = P.H, SS = P.SS;
+  const uint32_t cb = blockIdx.y * kOffsChunksPerBlock * kOffsTiles;
+  if (blockIdx.x * kOffsBlock >= H || cb >= SS) return;   // block-uniform
+  aes_lds_init<kOffsBlock>(te, g_aes.te0);
+  __syncthreads();
+  const AesLane A(te, threadIdx.x);
+  const uint32_t cend = min(SS, cb + kOffsChunksPerBlock * kOffsTiles);
+  // round 1's chunk-dependent half, once per chunk for the workgroup (pm_aes.h)
+  if (threadIdx.x < cend - cb) {
+    const R1Uniform u = r1_uniform(A, P.rk, cb + threadIdx.x);
+    r1u[threadIdx.x / kOffsChunksPerBlock][threadIdx.x % kOffsChunksPerBlock] = u;
+    r1u0[threadIdx.x / kOffsChunksPerBlock][threadIdx.x % kOffsChunksPerBlock] = u.u0;
+  }
+  __syncthreads();
+  const uint32_t h = blockIdx.x * kOffsBlock + threadIdx.x;
+  if (h >= H) return;
+  static_assert(kOffsChunksPerBlock == 8, "one 16-B tabT tile of 8 chunks per thread");
+  // SetSize <= 256: round 2's hint-only part once per hint (pm_aes.h r2_hint)
+  if (SS <= 256) {
+    if (P.tab) prep_offsets_tiles<true, true>(P, A, r1u, r1u0, cb, h);
+    else prep_offsets_tiles<true, false>(P, A, r1u, r1u0, cb, h);
+  } else {
+    if (P.tab) prep_offsets_tiles<false, true>(P, A, r1u, r1u0, cb, h);
+    else prep_offsets_tiles<false, false>(P, A, r1u, r1u0, cb, h);
   }
 }
 
@@ -1136,7 +1205,7 @@ __global__ void __launch_bounds__(kBlock) k_prf_batch(const uint32_t* __restrict
                                                       uint64_t* __restrict__ out) {
   __shared__ uint32_t te[kTeLdsWords];
   __shared__ uint32_t srk[44];
-  aes_lds_init(te, g_aes.te0);
+  aes_lds_init<kBlock>(te, g_aes.te0);
   if (threadIdx.x < 44) srk[threadIdx.x] = rk[threadIdx.x];
   __syncthreads();
   const AesLane A(te, threadIdx.x);
