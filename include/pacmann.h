@@ -118,6 +118,13 @@ int pm_timing_enable(pm_ctx* ctx, int level);
  * is created; its clients and sessions share the image and the decision.
  * "host_fold_rot512p" counts the folds over a packed image, "host_fold_rot512"
  * those over a plain one.
+ * "fold_bits": whether such a DB whose coordinates also have a clear sign and
+ * equal exponent bits 6..3 (f32 holding 0..255), or whose neighbour ids are
+ * below 2^20, gets a bit-packed fold image of 12-bit coordinate and / or 20-bit
+ * id fields where that has fewer 32-B slices than the packed image (1) or stays
+ * with the packed image (0); -1: PM_FOLD_BITS (default on); any other value is
+ * PM_EINVAL.  Read with "fold_pack", which must be on.  "host_fold_rot512q"
+ * counts the folds over a bit-packed image; its total adds up their slices.
  * "answer_pack": whether such a graph DB (zero low halves in every coordinate
  * word, E % 4 == 0, E <= 256 words, dim % 8 == 0) also gets a packed row image
  * (rows of 2 dim + 4 (2E - dim) bytes: the coordinates' high halves, then the

@@ -351,7 +351,7 @@ def prf_batch(rk: np.ndarray, tags, xs, ctx: Context | None = None) -> np.ndarra
 def set_option(name: str, value: int) -> None:
     """pm_set_option: choose among equivalent kernel paths process-wide
     ("match_part", "match_part8", "match_resolve"; -2 restores the default;
-    "aes_bs", "fold_rot", "fold_pack" and "answer_pack" 1 / 0, -1 restores the default)."""
+    "aes_bs", "fold_rot", "fold_pack", "fold_bits" and "answer_pack" 1 / 0, -1 restores the default)."""
     _check(lib().pm_set_option(name.encode(), int(value)))
 
 

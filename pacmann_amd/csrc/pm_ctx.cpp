@@ -159,6 +159,11 @@ extern "C" int pm_set_option(const char* name, int value) {
     pmk::set_fold_pack(value);
     return 0;
   }
+  if (!strcmp(name, "fold_bits")) {
+    if (value < -1 || value > 1) return fail(PM_EINVAL, "fold_bits takes 1, 0 or -1");
+    pmk::set_fold_bits(value);
+    return 0;
+  }
   if (!strcmp(name, "answer_pack")) {
     if (value < -1 || value > 1) return fail(PM_EINVAL, "answer_pack takes 1, 0 or -1");
     pmk::set_answer_pack(value);

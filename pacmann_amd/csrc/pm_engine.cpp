@@ -153,20 +153,29 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
   const bool fold_img = !remote && !g->owned_list.empty() && pmk::fold_image_ok(g->minCS, g->maxCS, (uint32_t)g->E);
   const uint32_t want_npk = !server && fold_img ? pmk::fold_pack_slices(g->minCS, g->maxCS, (uint32_t)g->E, coord_words) : 0;
   const uint32_t want_apk = !server && !remote && !g->owned_list.empty() ? pmk::answer_pack_segs((uint32_t)g->E, coord_words) : 0;
+  // The same pass looks at the other bits that are the same in every row of
+  // such a DB (the coordinates' sign and copied exponent bits, the ids' bits
+  // above 19): where they allow a bit-packed image of fewer slices, the server
+  // builds that one instead (FOLD_ROT512Q, pmk::fold_bits_form).
   bool low_zero = false;
+  uint32_t row_bits = 0;
   if (want_npk || want_apk) {
     DevBuf flag;
     CHK(flag.reserve(64));
-    low_zero = pmk::coord_low_zero(ctx->stream, g->db->as<uint64_t>(), off_db, (uint32_t)g->E, coord_words, flag.as<uint32_t>());
+    row_bits = pmk::row_bits_or(ctx->stream, g->db->as<uint64_t>(), off_db, (uint32_t)g->E, coord_words, flag.as<uint32_t>());
+    low_zero = !(row_bits & pmk::kRowLowHalf);
     HIPCHK(hipGetLastError());
   }
   if (fold_img) {
-    if (server) g->img_npk = server->img_npk;
-    else if (low_zero) g->img_npk = want_npk;
+    if (server) { g->img_npk = server->img_npk; g->img_bits = server->img_bits; }
+    else if (low_zero) {
+      g->img_bits = pmk::fold_bits_form((uint32_t)g->E, coord_words, want_npk, row_bits);
+      g->img_npk = g->img_bits ? 0 : want_npk;
+    }
     for (uint32_t i : g->owned_list) {
       PmPart& d = g->parts[i].d;
       d.img = (const uint64_t*)(uintptr_t)off_img;
-      off_img += pmk::fold_image_words(d.SS, (uint32_t)g->E, (uint32_t)g->maxCS, g->img_npk);
+      off_img += pmk::fold_image_words(d.SS, (uint32_t)g->E, (uint32_t)g->maxCS, g->img_npk, g->img_bits);
     }
     size_t free_b = 0, total_b = 0;
     if (!server && hipMemGetInfo(&free_b, &total_b) == hipSuccess && off_img * 8 > free_b / 4) {
@@ -176,7 +185,7 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
       for (uint32_t i : g->owned_list) g->parts[i].d.img = nullptr;
       off_img = 0;
     }
-    if (!off_img) g->img_npk = 0;
+    if (!off_img) g->img_npk = g->img_bits = 0;
   }
   if (off_img) {
     if (server) {
@@ -186,7 +195,7 @@ int engine_create(pm_ctx* ctx, Engine* g, uint64_t N, uint64_t Ebytes, uint64_t 
       for (uint32_t i : g->owned_list) {
         const PmPart& d = g->parts[i].d;
         pmk::fold_image(ctx->stream, g->img->as<uint64_t>() + (uintptr_t)d.img, g->db->as<uint64_t>() + d.row0 * g->E,
-                        d.N, d.SS, (uint32_t)g->E, (uint32_t)g->maxCS, g->img_npk);
+                        d.N, d.SS, (uint32_t)g->E, (uint32_t)g->maxCS, g->img_npk, g->img_bits);
       }
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -404,9 +413,11 @@ int engine_prep_launch(pm_ctx* c, const Engine* g, const PmPart* dp, int np, con
     int kind = pmk::FOLD_GATHER;
     c->timed("prep_fold", fold, [&] { kind = pmk::prep_fold(st, dp, np, g->maxH, g->db->as<uint64_t>(), (uint32_t)g->E, g->minCS,
                                                       g->maxCS, g->zero16.as<uint64_t>(), clients, g->img->p != nullptr, minH,
-                                                      g->img_npk); });
-    if (kind == pmk::FOLD_ROT512 || kind == pmk::FOLD_ROT512P || kind == pmk::FOLD_ROT1024) {
-      c->host_add(kind == pmk::FOLD_ROT512 ? HT_FOLD_ROT512 : kind == pmk::FOLD_ROT512P ? HT_FOLD_ROT512P : HT_FOLD_ROT1024, 0.0);
+                                                      g->img_npk, g->img_bits); });
+    if (kind == pmk::FOLD_ROT512 || kind == pmk::FOLD_ROT512P || kind == pmk::FOLD_ROT512Q || kind == pmk::FOLD_ROT1024) {
+      c->host_add(kind == pmk::FOLD_ROT512 ? HT_FOLD_ROT512 : kind == pmk::FOLD_ROT512P ? HT_FOLD_ROT512P
+                  : kind == pmk::FOLD_ROT512Q ? HT_FOLD_ROT512Q : HT_FOLD_ROT1024,
+                  kind == pmk::FOLD_ROT512Q ? (double)pmk::fold_bits_slices(g->img_bits, (uint32_t)g->E) : 0.0);
     } else {
       c->host_add(HT_FOLD_OTHER, 0.0);
       c->host_add(kind == pmk::FOLD_PIPE ? HT_FOLD_PIPE : kind == pmk::FOLD_BLK ? HT_FOLD_BLK : HT_FOLD_GATHER, 0.0);

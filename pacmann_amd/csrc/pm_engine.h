@@ -231,6 +231,7 @@ struct Engine {
   std::shared_ptr<DevBuf> db = std::make_shared<DevBuf>();   // server DB; shared by the clients of pm_batchpir_create_client
   std::shared_ptr<DevBuf> img = std::make_shared<DevBuf>();  // the DB's fold image (pmk::fold_image), shared likewise
   uint32_t img_npk = 0;   // its packed coordinate slices (FOLD_ROT512P; 0: a plain image), the server's for a client
+  uint32_t img_bits = 0;  // its bit-packed fields (FOLD_ROT512Q, pmk::fold_bits_form; then img_npk is 0), the server's for a client
   // the DB's packed row image for the pair answer (pmk::answer_pack_image), shared likewise; its 16-B segments
   // per row (0: no image) and how many of them are coordinates.  step_db puts them into a step.
   std::shared_ptr<DevBuf> apk = std::make_shared<DevBuf>();

@@ -120,7 +120,10 @@ struct HostBuf {
 // rank (failed), by another rank's sub-query (peer), or not at all (unexplained).
 // "host_fold_*" count the maintenance fold launches by form (pmk::fold_form):
 // "rot512" / "rot1024" k_prep_fold_rot at CS 512 / 1,024, "rot512p" the same
-// kernel at CS 512 over a packed image (FOLD_ROT512P); "other" every launch
+// kernel at CS 512 over a packed image (FOLD_ROT512P), "rot512q" over a
+// bit-packed one (FOLD_ROT512Q; its total_ms adds up the slices each launch
+// folded, a count: 9 for SIFT1M's rows, 11 with 12-bit coordinates or 20-bit
+// ids alone); "other" every launch
 // that is not a rotated one, which "pipe" (k_prep_fold_pipe), "blk"
 // (k_prep_fold_blk, one count for its full-width and remainder launches) and
 // "gather" (the unblocked k_prep_fold<W>, E < 4 included) split by kernel
@@ -137,8 +140,8 @@ struct HostBuf {
 // _finish, one entry per call that ran (a refused call counts nothing).
 // "host_prep_stream": the wall time of a streamed preprocessing from pm_batchpir_prep_stream_begin to _end, one
 // entry per completed stream; "host_prep_stream_windows": the sub-windows its rows went up in (a count).
-enum HostTimer : int { HT_STEP_LAUNCH, HT_STEP_WAIT, HT_STEP_POST, HT_BATCH_QUERY, HT_GVI_PARSE, HT_SEARCH_KNN, HT_KNN_INIT, HT_KNN_BATCH, HT_KNN_UPDATE, HT_KNN_FINAL, HT_WAIT_FIRST, HT_WAIT_ALL, HT_ROWS_SEEN, HT_ROWS_TORN, HT_WAIT_DONE, HT_COMBINE, HT_COMBINE_TURN, HT_PATH_MATCH, HT_PATH_MATCH_PART, HT_PATH_MATCH_PART8, HT_PREP_SETS, HT_REC_VERIFIED, HT_REC_BAD, HT_REC_DROPPED, HT_REC_FAILED, HT_REC_PEER, HT_REC_UNEXPLAINED, HT_FOLD_ROT512, HT_FOLD_ROT1024, HT_FOLD_OTHER, HT_FOLD_PIPE, HT_FOLD_BLK, HT_FOLD_GATHER, HT_FOLD_ROT512P, HT_DEV_STEPS, HT_DEV_QUERIES, HT_KNN_BATCH_FALLBACK, HT_PATH_STEP, HT_PATH_RESOLVE_LDS, HT_PATH_RESOLVE_G, HT_PATH_MR_S2, HT_PATH_MR_S4, HT_PATH_MR_GENERAL, HT_PATH_GATHER, HT_PATH_ANSWER_P5, HT_PATH_ANSWER_P, HT_PATH_ANSWER_S, HT_PATH_ANSWER_G, HT_ANSWER_PACKED, HT_GVI_GROUP, HT_GVI_GROUP_STEPS, HT_SERVER_ANSWER_PACKED, HT_CLIENT_BEGIN, HT_CLIENT_FINISH, HT_PREP_STREAM, HT_PREP_STREAM_WINDOWS, HT_COUNT };
-static const char* const kHostTimerName[HT_COUNT] = {"host_step_launch", "host_step_wait", "host_step_post", "host_batch_query", "host_gvi_parse", "host_search_knn", "host_knn_init", "host_knn_batch", "host_knn_update", "host_knn_final", "host_wait_first_token", "host_wait_all_tokens", "host_rows_seen", "host_rows_torn", "host_wait_done", "host_combine", "host_combine_turn", "host_path_match", "host_path_match_part", "host_path_match_part8", "host_prep_sets", "host_records_verified", "host_records_bad", "host_records_dropped", "host_records_failed", "host_records_peer", "host_records_unexplained", "host_fold_rot512", "host_fold_rot1024", "host_fold_other", "host_fold_pipe", "host_fold_blk", "host_fold_gather", "host_fold_rot512p", "host_dev_steps", "host_dev_queries", "host_knn_batch_fallback", "host_path_step", "host_path_resolve_lds", "host_path_resolve_g", "host_path_mr_s2", "host_path_mr_s4", "host_path_mr_general", "host_path_gather", "host_path_answer_p5", "host_path_answer_p", "host_path_answer_s", "host_path_answer_g", "host_answer_packed", "host_gvi_group", "host_gvi_group_steps", "host_server_answer_packed", "host_client_begin", "host_client_finish", "host_prep_stream", "host_prep_stream_windows"};
+enum HostTimer : int { HT_STEP_LAUNCH, HT_STEP_WAIT, HT_STEP_POST, HT_BATCH_QUERY, HT_GVI_PARSE, HT_SEARCH_KNN, HT_KNN_INIT, HT_KNN_BATCH, HT_KNN_UPDATE, HT_KNN_FINAL, HT_WAIT_FIRST, HT_WAIT_ALL, HT_ROWS_SEEN, HT_ROWS_TORN, HT_WAIT_DONE, HT_COMBINE, HT_COMBINE_TURN, HT_PATH_MATCH, HT_PATH_MATCH_PART, HT_PATH_MATCH_PART8, HT_PREP_SETS, HT_REC_VERIFIED, HT_REC_BAD, HT_REC_DROPPED, HT_REC_FAILED, HT_REC_PEER, HT_REC_UNEXPLAINED, HT_FOLD_ROT512, HT_FOLD_ROT1024, HT_FOLD_OTHER, HT_FOLD_PIPE, HT_FOLD_BLK, HT_FOLD_GATHER, HT_FOLD_ROT512P, HT_FOLD_ROT512Q, HT_DEV_STEPS, HT_DEV_QUERIES, HT_KNN_BATCH_FALLBACK, HT_PATH_STEP, HT_PATH_RESOLVE_LDS, HT_PATH_RESOLVE_G, HT_PATH_MR_S2, HT_PATH_MR_S4, HT_PATH_MR_GENERAL, HT_PATH_GATHER, HT_PATH_ANSWER_P5, HT_PATH_ANSWER_P, HT_PATH_ANSWER_S, HT_PATH_ANSWER_G, HT_ANSWER_PACKED, HT_GVI_GROUP, HT_GVI_GROUP_STEPS, HT_SERVER_ANSWER_PACKED, HT_CLIENT_BEGIN, HT_CLIENT_FINISH, HT_PREP_STREAM, HT_PREP_STREAM_WINDOWS, HT_COUNT };
+static const char* const kHostTimerName[HT_COUNT] = {"host_step_launch", "host_step_wait", "host_step_post", "host_batch_query", "host_gvi_parse", "host_search_knn", "host_knn_init", "host_knn_batch", "host_knn_update", "host_knn_final", "host_wait_first_token", "host_wait_all_tokens", "host_rows_seen", "host_rows_torn", "host_wait_done", "host_combine", "host_combine_turn", "host_path_match", "host_path_match_part", "host_path_match_part8", "host_prep_sets", "host_records_verified", "host_records_bad", "host_records_dropped", "host_records_failed", "host_records_peer", "host_records_unexplained", "host_fold_rot512", "host_fold_rot1024", "host_fold_other", "host_fold_pipe", "host_fold_blk", "host_fold_gather", "host_fold_rot512p", "host_fold_rot512q", "host_dev_steps", "host_dev_queries", "host_knn_batch_fallback", "host_path_step", "host_path_resolve_lds", "host_path_resolve_g", "host_path_mr_s2", "host_path_mr_s4", "host_path_mr_general", "host_path_gather", "host_path_answer_p5", "host_path_answer_p", "host_path_answer_s", "host_path_answer_g", "host_answer_packed", "host_gvi_group", "host_gvi_group_steps", "host_server_answer_packed", "host_client_begin", "host_client_finish", "host_prep_stream", "host_prep_stream_windows"};
 static_assert(HT_PATH_ANSWER_G - HT_PATH_STEP + 1 == pmk::FORM_COUNT, "one counter per step form, in the order of pmk::FORM_*");
 
 struct TimedLaunch { std::string name; hipEvent_t a, b; double bytes; };

@@ -371,19 +371,22 @@ void set_aes_bs(int v);
 // FOLD_ROT512P is k_prep_fold_rot<512> over a packed image: the DB is a graph
 // DB whose coordinate words (f32 holding small integers, e.g. SIFT's bytes) all
 // have zero low halves, so the image and the fold leave those halves out.
-enum : int { FOLD_GATHER = 0, FOLD_ROT512 = 1, FOLD_ROT1024 = 2, FOLD_PIPE = 3, FOLD_BLK = 4, FOLD_ROT512P = 5 };
+// FOLD_ROT512Q is the same kernel over a bit-packed image: such a DB whose
+// coordinates are f32 holding 0..255 and / or whose ids are below 2^20 also has
+// constant exponent, sign and high id bits, which the image leaves out too.
+enum : int { FOLD_GATHER = 0, FOLD_ROT512 = 1, FOLD_ROT1024 = 2, FOLD_PIPE = 3, FOLD_BLK = 4, FOLD_ROT512P = 5, FOLD_ROT512Q = 6 };
 // The one selection of the form: from the partitions' ChunkSize range, the entry
 // words, whether the engine was created with a fold image and the image's packed
-// coordinate slices (npk, 0: a plain image).  prep_fold dispatches on it and
-// fold_needs_tab follows from it.
-int fold_form(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img, uint32_t npk = 0);
+// coordinate slices (npk, 0: a plain image) or bit-packed fields (qf, 0: none).
+// prep_fold dispatches on it and fold_needs_tab follows from it.
+int fold_form(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img, uint32_t npk = 0, uint32_t qf = 0);
 // "fold_rot": 1 / 0 the rotated fold and its image for engines created from now
 // on, -1 = PM_FOLD_ROT's value (default on).  Consulted by fold_image_ok only,
 // i.e. when an engine is created; an existing engine keeps its form.
 void set_fold_rot(int v);
 int prep_fold(hipStream_t st, const PmPart* dparts, int nparts, uint32_t maxH, const uint64_t* db,
               uint32_t E, uint32_t minCS, uint32_t maxCS, const uint64_t* zero16, uint32_t clients = 1,
-              bool have_img = false, uint32_t minH = 0, uint32_t npk = 0);
+              bool have_img = false, uint32_t minH = 0, uint32_t npk = 0, uint32_t qf = 0);
 void prep_repl(hipStream_t st, const PmPart* dparts, int nparts, uint32_t maxRepl,
                const uint64_t* db, uint32_t E);
 // The streamed preprocessing (pm_stream.hip; pm_batchpir_prep_stream_rows): UpdatePreprocessing of chunks
@@ -403,21 +406,33 @@ bool fold_image_ok(uint32_t minCS, uint32_t maxCS, uint32_t E);
 // whether the fold of these shapes reads the chunk-major PRF table PmPart::tab
 // (otherwise it is not allocated: every other reader uses tabT)
 bool fold_needs_tab(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img);
-uint64_t fold_image_words(uint32_t SS, uint32_t E, uint32_t CS, uint32_t npk = 0);
+uint64_t fold_image_words(uint32_t SS, uint32_t E, uint32_t CS, uint32_t npk = 0, uint32_t qf = 0);
 void fold_image(hipStream_t st, uint64_t* img, const uint64_t* part_rows, uint64_t N, uint32_t SS, uint32_t E,
-                uint32_t CS, uint32_t npk = 0);
+                uint32_t CS, uint32_t npk = 0, uint32_t qf = 0);
 // The packed image.  fold_pack_shape: the packed coordinate slices of entries of
 // E words whose first `dim` 32-bit words are coordinates (16 per slice), 0 where
 // they do not fill whole slices of the folded words.  fold_pack_slices: the same
 // for an engine being created, 0 also unless its fold is FOLD_ROT512 and
 // "fold_pack" / PM_FOLD_PACK (1 / 0, -1 the environment's, default on) allows
-// it.  coord_low_zero: one reduction over the packed DB rows, true if the low
-// half of every coordinate word of every row is zero (flag: 4 device bytes;
-// false on a HIP error too).  Both are asked once, when a server packs its DB.
+// it.  "fold_bits" / PM_FOLD_BITS (the same values, default on) allows the
+// bit-packed image on top of it; off, such a DB takes the packed image.
+// row_bits_or: one reduction over the packed DB rows for the bits the images
+// leave out: kRowLowHalf if the low half of a coordinate word is not zero,
+// kRowCoordBits if a coordinate's sign is set or its exponent bits 6..3 are not
+// all equal, kRowIdBits if a later word has a bit above 19 set (flag: 4 device
+// bytes; every flag on a HIP error).  fold_bits_form: the bit-packed image's
+// fields for a DB with those flags whose packed image has npk slices (w1 | w2
+// << 8 | dim / 4 << 16: 12- or 16-bit coordinate and 20- or 32-bit id fields),
+// 0 where none has fewer slices or "fold_bits" is off; fold_bits_slices: its
+// slices.  All are asked once, when a server packs its DB.
+enum : uint32_t { kRowLowHalf = 1, kRowCoordBits = 2, kRowIdBits = 4 };
 void set_fold_pack(int v);
+void set_fold_bits(int v);
 uint32_t fold_pack_shape(uint32_t E, uint32_t dim);
 uint32_t fold_pack_slices(uint32_t minCS, uint32_t maxCS, uint32_t E, uint32_t dim);
-bool coord_low_zero(hipStream_t st, const uint64_t* rows, uint64_t nrows, uint32_t E, uint32_t dim, uint32_t* flag);
+uint32_t row_bits_or(hipStream_t st, const uint64_t* rows, uint64_t nrows, uint32_t E, uint32_t dim, uint32_t* flag);
+uint32_t fold_bits_form(uint32_t E, uint32_t dim, uint32_t npk, uint32_t flags);
+uint32_t fold_bits_slices(uint32_t qf, uint32_t E);
 // The answer's packed row image (k_answer_p5k / k_answer_pk): for the same kind of
 // DB, a row-major copy of the rows without the coordinates' low halves: row r =
 // the high halves of its `dim` coordinate words as consecutive half-words, then

@@ -611,6 +611,106 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_pipe(const PmPart* _
 // halves are zero in every row of the DB and so in every parity; the id slices
 // follow.  The fold itself does not differ: a lane's 8 accumulators of a packed
 // slice are 16 half-words, which the epilogue expands to 16 parity dwords (64 B).
+// qf != 0 (CS 512 only, FOLD_ROT512Q): the image is bit-packed (fold_bits_*
+// below, k_fold_image_bits).  The fold does not differ either; the epilogue
+// takes the fields of a lane's 256 accumulated bits apart and stores each quad
+// of four as four whole parity dwords.
+//
+// The bit-packed image.  A row's folded 32-bit words are taken four at a time
+// (a quad: one aligned 16-B store of the parity): first n1 coordinate quads of
+// w1-bit fields, then n2 quads of w2-bit fields for the words that follow (the
+// neighbour ids).  A field is a selection of its word's bits, the others being
+// the same in every row of the DB (k_row_bits_or), so the same in every XOR of
+// rows:
+//   w1 = 12  half-word bits 14 (exponent bit 7), 10 (exponent bit 3, which bits
+//            4..6 copy) and 9..0; the sign and the low half are zero
+//   w1 = 16  the high half-word (the fields of FOLD_ROT512P)
+//   w2 = 20  bits 19..0 (ids below 2^20)      w2 = 32  the whole word
+// A 32-B slice holds whole quads, so that every parity dword is written by one
+// workgroup: 64 / w1 coordinate quads per slice from bit 0 up (quad i, field t
+// at bit (4 i + t) w1), then one slice with the coordinate quads left over and
+// as many of the others as still fit, then 64 / w2 of the others per slice.
+// Those lie from bit 256 down (quad i, field t at bit 256 - 4 w2 (i + 1) + t
+// w2): every field sits at a place known when the kernel is compiled, whatever
+// the slice holds.  SIFT1M (12, 20): 6 slices of 20 coordinates, one of 8
+// coordinates and 8 ids, two of 12 ids: 9 slices where FOLD_ROT512P has 12.
+// qf = w1 | w2 << 8 | n1 << 16; n2 follows from the folded words.
+struct FoldBits { uint32_t w1, n1, w2, n2; };
+struct FoldBitsSlice { uint32_t q1, c1, q2, c2; };   // first quad and quads of each kind in a slice
+__host__ __device__ inline FoldBits fold_bits_of(uint32_t qf, uint32_t E) {
+  FoldBits f;
+  f.w1 = qf & 0xffu; f.w2 = (qf >> 8) & 0xffu; f.n1 = qf >> 16;
+  f.n2 = (E & ~3u) / 2 - f.n1;
+  return f;
+}
+__host__ __device__ inline FoldBitsSlice fold_bits_slice(const FoldBits& f, uint32_t s) {
+  const uint32_t per1 = 64 / f.w1, per2 = 64 / f.w2, nf1 = f.n1 / per1, r1 = f.n1 % per1;
+  const uint32_t fit = r1 ? (64 - r1 * f.w1) / f.w2 : 0u, cm = fit < f.n2 ? fit : f.n2;   // the others beside the left-over coordinates
+  FoldBitsSlice o;
+  if (s < nf1) { o.q1 = s * per1; o.c1 = per1; o.q2 = 0; o.c2 = 0; return o; }
+  if (r1 && s == nf1) { o.q1 = nf1 * per1; o.c1 = r1; o.q2 = 0; o.c2 = cm; return o; }
+  o.q1 = f.n1; o.c1 = 0;
+  o.q2 = cm + (s - nf1 - (r1 ? 1 : 0)) * per2;
+  o.c2 = o.q2 >= f.n2 ? 0u : f.n2 - o.q2 < per2 ? f.n2 - o.q2 : per2;
+  return o;
+}
+__host__ __device__ inline uint32_t fold_bits_nsl(const FoldBits& f) {
+  const uint32_t per1 = 64 / f.w1, per2 = 64 / f.w2, nf1 = f.n1 / per1, r1 = f.n1 % per1;
+  const uint32_t fit = r1 ? (64 - r1 * f.w1) / f.w2 : 0u, cm = fit < f.n2 ? fit : f.n2;
+  return nf1 + (r1 ? 1 : 0) + (f.n2 - cm + per2 - 1) / per2;
+}
+template <int W> __host__ __device__ __forceinline__ uint32_t fold_field_pack(uint32_t x) {
+  if constexpr (W == 12) return ((x >> 16) & 0x7ffu) | ((x >> 19) & 0x800u);
+  else if constexpr (W == 16) return x >> 16;
+  else if constexpr (W == 20) return x & 0xfffffu;
+  else return x;
+}
+template <int W> __host__ __device__ __forceinline__ uint32_t fold_field_expand(uint32_t f) {
+  if constexpr (W == 12) return ((f & 0x7ffu) | ((f & 0x400u) * 14u) | ((f & 0x800u) << 3)) << 16;
+  else if constexpr (W == 16) return f << 16;
+  else return f;
+}
+// field of W bits at bit p of a slice's eight dwords (p: a constant once the callers' loops are unrolled)
+template <int W> __device__ __forceinline__ uint32_t fold_bits_get(const uint32_t (&d)[8], int p) {
+  const int i = p >> 5, sh = p & 31;
+  uint32_t v = d[i] >> sh;
+  if (sh + W > 32) v |= d[i + 1] << (32 - sh);
+  if constexpr (W < 32) v &= (1u << W) - 1u;
+  return v;
+}
+template <int W> __device__ __forceinline__ void fold_bits_put(uint32_t (&d)[8], int p, uint32_t f) {
+  const int i = p >> 5, sh = p & 31;
+  d[i] |= f << sh;
+  if (sh + W > 32) d[i + 1] |= f >> (32 - sh);
+}
+__host__ __device__ constexpr int fold_bits_pos1(int w1, int i, int t) { return (4 * i + t) * w1; }
+__host__ __device__ constexpr int fold_bits_pos2(int w2, int i, int t) { return 256 - 4 * w2 * (i + 1) + t * w2; }
+// the epilogue of a bit-packed slice: d, the slice's accumulated dwords in the image's order
+template <int W1, int W2>
+__device__ __forceinline__ void fold_bits_store(const uint32_t (&d)[8], const FoldBitsSlice& sl, uint32_t n1,
+                                                PM_G uint32_t* par) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+  for (int i = 0; i < 64 / W1; ++i) {
+    if ((uint32_t)i >= sl.c1) break;   // block-uniform
+    u32x4 x;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) x[t] = fold_field_expand<W1>(fold_bits_get<W1>(d, fold_bits_pos1(W1, i, t)));
+    PM_G u32x4* const dst = reinterpret_cast<PM_G u32x4*>(par + (sl.q1 + i) * 4);
+    if (PM_PREP_NT) __builtin_nontemporal_store(x, dst);
+    else *dst = x;
+  }
+#pragma unroll
+  for (int i = 0; i < 64 / W2; ++i) {
+    if ((uint32_t)i >= sl.c2) break;   // block-uniform
+    u32x4 x;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) x[t] = fold_field_expand<W2>(fold_bits_get<W2>(d, fold_bits_pos2(W2, i, t)));
+    PM_G u32x4* const dst = reinterpret_cast<PM_G u32x4*>(par + (n1 + sl.q2 + i) * 4);
+    if (PM_PREP_NT) __builtin_nontemporal_store(x, dst);
+    else *dst = x;
+  }
+}
 #ifndef PM_ROT_HPL
 #define PM_ROT_HPL 5
 #endif
@@ -619,6 +719,12 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_pipe(const PmPart* _
 #endif                // (64 clients, one box: 4 x 8 19.4 ms, 8 x 4 20.2, 16 x 2 +2 %)
 #ifndef PM_ROT_SB
 #define PM_ROT_SB 8
+#endif
+#ifndef PM_ROTQ_GB
+#define PM_ROTQ_GB 4   // the bit-packed image's tile (SIFT1M's 9 slices in one slice block; 288 clients, one box:
+#endif                // 4 x 9 51.6 ms, 4 x 8 51.8, 3 x 9 52.6, 6 x 5 52.8, 11 x 3 55.1; profiles/r14)
+#ifndef PM_ROTQ_SB
+#define PM_ROTQ_SB 9
 #endif
 #ifndef PM_ROT_HPL2
 #define PM_ROT_HPL2 7   // hints per lane at CS 1,024 (2-B tiles; 128 VGPRs, no spills): 140 / 126 / 118 ms at 5 / 6 / 7
@@ -630,7 +736,8 @@ __host__ __device__ constexpr uint32_t rot_nch(uint32_t cs) { return cs == 512 ?
 template <int CS>
 __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __restrict__ parts, uint32_t E,
                                                                 uint32_t nvg, uint32_t nsl, uint32_t npv,
-                                                                uint32_t npk_arg, uint32_t K, uint32_t ngc) {
+                                                                uint32_t npk_arg, uint32_t K, uint32_t ngc,
+                                                                uint32_t qf_arg, uint32_t GB, uint32_t SB) {
   constexpr uint32_t NCH = rot_nch(CS), LINE = NCH * 8, BUFW = (CS + 1) * LINE;
   constexpr int HPL = rot_hpl(CS);
   static_assert(CS == 512 || CS == 1024, "4 chunks of 512 rows or 2 of 1,024 per block");
@@ -651,9 +758,11 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
   // mixing).
   constexpr uint32_t HB = kFoldThreads * HPL;
   const uint32_t npk = CS == 512 ? npk_arg : 0u;   // packed coordinate slices (nsl counts packed slices)
+  const uint32_t qf = CS == 512 ? qf_arg : 0u;     // the bit-packed image's fields (nsl counts its slices; npk is 0)
   const uint32_t xcd = blockIdx.x % 8, kq = blockIdx.x / 8;
-  // Order: tiles of GB consecutive (partition, group) pairs x SB consecutive slices,
-  // one tile per XCD at a time (GB * SB = its 32 CUs): a group's tabT rows are
+  // Order: tiles of GB consecutive (partition, group) pairs x SB consecutive slices
+  // (GB and SB: kernel arguments, prep_fold chooses them by form), one tile per XCD at a time (GB * SB: about
+  // its 32 CUs): a group's tabT rows are
   // read by SB workgroups and a slice's image blocks by GB workgroups out of
   // the XCD's L2.  The eight XCDs take eight consecutive pair blocks of the
   // SAME slice block, so the partition's image slices are shared through the
@@ -662,7 +771,6 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
   // Tile T = (its index on the XCD) * 8 + XCD; a last group of fewer than 8
   // pair blocks is dealt over the XCDs the same way (small launches, e.g. one
   // client's 48 pairs, keep every XCD busy).
-  constexpr uint32_t GB = PM_ROT_GB, SB = PM_ROT_SB;
   const uint32_t nsb = (nsl + SB - 1) / SB, ngb = (npv + GB - 1) / GB;
   const uint32_t T = (kq / (GB * SB)) * 8 + xcd, wt = kq % (GB * SB);
   if (T >= ngb * nsb) return;   // block-uniform
@@ -788,7 +896,20 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
     const bool inB = v >= vb;
     PM_G uint64_t* const par = (inB ? PB.parity : PA.parity) + (uint64_t)(v - (inB ? vb : hA)) * E;
     PM_G uint32_t* dst = reinterpret_cast<PM_G uint32_t*>(par + w);
-    if (slice < npk) {   // block-uniform: half-word i of the slice is the high half of parity dword i
+    if (qf) {   // block-uniform: the slice's 256 bits in the image's order, then field by field
+      uint32_t d[8];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        d[t] = j ? acc[k][4 + t] : acc[k][t];
+        d[4 + t] = j ? acc[k][t] : acc[k][4 + t];
+      }
+      const FoldBits fb = fold_bits_of(qf, E);
+      const FoldBitsSlice sl = fold_bits_slice(fb, slice);
+      PM_G uint32_t* const p32 = reinterpret_cast<PM_G uint32_t*>(par);
+      if (fb.w1 == 12 && fb.w2 == 20) fold_bits_store<12, 20>(d, sl, fb.n1, p32);
+      else if (fb.w1 == 16) fold_bits_store<16, 20>(d, sl, fb.n1, p32);
+      else fold_bits_store<12, 32>(d, sl, fb.n1, p32);
+    } else if (slice < npk) {   // block-uniform: half-word i of the slice is the high half of parity dword i
       typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
       for (int t = 0; t < 8; t += 2) {   // accumulators t, t + 1: dwords 2 p .. 2 p + 3 of the 16, p the word's place
@@ -805,7 +926,7 @@ __global__ void __launch_bounds__(kFoldThreads) k_prep_fold_rot(const PmPart* __
         else *d = acc[k][t];
       }
     }
-    if (w == 0)   // xorSlices leaves the words past len&~3 zero
+    if (slice == 0)   // xorSlices leaves the words past len&~3 zero
       for (uint32_t t = E & ~3u; t < E; ++t) par[t] = 0;
   }
 }
@@ -846,6 +967,48 @@ __global__ void __launch_bounds__(kBlock) k_fold_image(uint4* __restrict__ img, 
     img[x] = v;
   }
 }
+// The bit-packed image (fold_bits_*): the same blocks, lines, chunk slots and
+// halves; a thread packs its row's slice and keeps its item's half of it.
+template <int W1, int W2>
+__device__ __forceinline__ void fold_bits_pack(const uint32_t* __restrict__ row, const FoldBitsSlice& sl, uint32_t n1,
+                                               uint32_t (&d)[8]) {
+#pragma unroll
+  for (int i = 0; i < 64 / W1; ++i) {
+    if ((uint32_t)i >= sl.c1) break;
+    const uint4 v = *reinterpret_cast<const uint4*>(row + (sl.q1 + i) * 4);
+    const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) fold_bits_put<W1>(d, fold_bits_pos1(W1, i, t), fold_field_pack<W1>(x[t]));
+  }
+#pragma unroll
+  for (int i = 0; i < 64 / W2; ++i) {
+    if ((uint32_t)i >= sl.c2) break;
+    const uint4 v = *reinterpret_cast<const uint4*>(row + (n1 + sl.q2 + i) * 4);
+    const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) fold_bits_put<W2>(d, fold_bits_pos2(W2, i, t), fold_field_pack<W2>(x[t]));
+  }
+}
+__global__ void __launch_bounds__(kBlock) k_fold_image_bits(uint4* __restrict__ img, const uint64_t* __restrict__ rows,
+                                                           uint64_t N, uint32_t nbuf, uint32_t E, uint64_t nitems,
+                                                           uint32_t qf) {
+  const FoldBits fb = fold_bits_of(qf, E);
+  for (uint64_t x = (uint64_t)blockIdx.x * kBlock + threadIdx.x; x < nitems; x += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t it = (uint32_t)(x % (kRotBufBytes / 16));
+    const uint64_t blk = x / (kRotBufBytes / 16);
+    const uint32_t b = (uint32_t)(blk % nbuf), s = (uint32_t)(blk / nbuf);
+    const uint64_t r = (uint64_t)(4 * b + ((it >> 1) & 3)) * 512 + (it >> 3);
+    uint32_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (r < N) {
+      const uint32_t* const row = reinterpret_cast<const uint32_t*>(rows + r * E);
+      const FoldBitsSlice sl = fold_bits_slice(fb, s);
+      if (fb.w1 == 12 && fb.w2 == 20) fold_bits_pack<12, 20>(row, sl, fb.n1, d);
+      else if (fb.w1 == 16) fold_bits_pack<16, 20>(row, sl, fb.n1, d);
+      else fold_bits_pack<12, 32>(row, sl, fb.n1, d);
+    }
+    img[x] = (it & 1) ? make_uint4(d[4], d[5], d[6], d[7]) : make_uint4(d[0], d[1], d[2], d[3]);
+  }
+}
 // The answer's packed row image (pmk::answer_pack_image): item x = 16-B segment
 // x % nseg of row x / nseg.  The first cseg segments hold the high halves of
 // eight coordinate words each (the packing of k_fold_image), the others four
@@ -868,19 +1031,34 @@ __global__ void __launch_bounds__(kBlock) k_answer_pack_image(uint4* __restrict_
     img[x] = v;
   }
 }
-// OR of the low halves of the coordinate words (32-bit words [0, dim) of every
-// E-word row; dim % 4 == 0, E even): *out becomes non-zero if any is non-zero
-__global__ void __launch_bounds__(kBlock) k_coord_low_or(const uint64_t* __restrict__ rows, uint64_t nrows, uint32_t E,
-                                                        uint32_t dim, uint32_t* __restrict__ out) {
-  const uint32_t per = dim / 4;
+// One pass over the rows for the bits that the packed images leave out (32-bit
+// words [0, dim) of every E-word row are coordinates, the others ids; dim % 4 ==
+// 0, E even).  *out gets kRowLowHalf if a coordinate word has a non-zero low
+// half, kRowCoordBits if one has its sign set or exponent bits 6..3 not all
+// equal (an f32 holding 0..255 has neither: its exponent is 0 or 127..134), and
+// kRowIdBits if another word has one of bits 31..20 set.
+__device__ inline uint32_t coord_bits_or(uint32_t x) {
+  const uint32_t e6 = x >> 29;
+  return (x >> 31) | ((((e6 ^ (x >> 28)) | (e6 ^ (x >> 27)) | (e6 ^ (x >> 26))) & 1u));
+}
+__global__ void __launch_bounds__(kBlock) k_row_bits_or(const uint64_t* __restrict__ rows, uint64_t nrows, uint32_t E,
+                                                       uint32_t dim, uint32_t* __restrict__ out) {
+  const uint32_t per = E / 2;
   const uint64_t nitems = nrows * per;
-  uint32_t acc = 0;
+  uint32_t low = 0, cb = 0, ib = 0;
   for (uint64_t x = (uint64_t)blockIdx.x * kBlock + threadIdx.x; x < nitems; x += (uint64_t)gridDim.x * kBlock) {
     const uint64_t r = x / per;
-    const uint4 v = reinterpret_cast<const uint4*>(rows + r * E)[x - r * per];
-    acc |= v.x | v.y | v.z | v.w;
+    const uint32_t i = (uint32_t)(x - r * per);
+    const uint4 v = reinterpret_cast<const uint4*>(rows + r * E)[i];
+    if (4 * i < dim) {
+      low |= v.x | v.y | v.z | v.w;
+      cb |= coord_bits_or(v.x) | coord_bits_or(v.y) | coord_bits_or(v.z) | coord_bits_or(v.w);
+    } else {
+      ib |= v.x | v.y | v.z | v.w;
+    }
   }
-  if (acc & 0xffffu) atomicOr(out, 1u);
+  const uint32_t f = ((low & 0xffffu) ? pmk::kRowLowHalf : 0u) | (cb ? pmk::kRowCoordBits : 0u) | ((ib >> 20) ? pmk::kRowIdBits : 0u);
+  if (f) atomicOr(out, f);
 }
 
 // Replacement rows (pir.go:345-350): Qpc random offsets per chunk, idx + copy.
@@ -1288,10 +1466,10 @@ static uint32_t fold_blk_sw(uint32_t maxCS) {
   while (sw > 2 && !fits(sw)) sw /= 2;
   return fits(sw) ? sw : 0;
 }
-int fold_form(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img, uint32_t npk) {
+int fold_form(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img, uint32_t npk, uint32_t qf) {
   if ((E & ~3u) == 0) return FOLD_GATHER;   // xorSlices folds nothing: zero parities
   if (have_img && fold_rot_shape(minCS, maxCS, E))
-    return maxCS == 512 ? (npk ? FOLD_ROT512P : FOLD_ROT512) : FOLD_ROT1024;
+    return maxCS == 512 ? (qf ? FOLD_ROT512Q : npk ? FOLD_ROT512P : FOLD_ROT512) : FOLD_ROT1024;
   if (minCS == maxCS && (maxCS == 512 || maxCS == 1024 || maxCS == 2048) && E % 2 == 0) return FOLD_PIPE;
   if (E % 2 || !fold_blk_sw(maxCS)) return FOLD_GATHER;   // odd entries or very wide chunks
   return FOLD_BLK;
@@ -1304,16 +1482,45 @@ bool fold_needs_tab(uint32_t minCS, uint32_t maxCS, uint32_t E, bool have_img) {
 }
 static std::atomic<int> g_fold_pack{-1};
 void set_fold_pack(int v) { g_fold_pack.store(v < 0 ? -1 : (v ? 1 : 0)); }
-// Like "fold_rot", "fold_pack" (else PM_FOLD_PACK, default on) is read here
-// only, while a server's image is built; its clients share the image and so the
-// decision.  Whole packed slices: 16 coordinate words each, inside the folded
-// E & ~3 words.
-uint32_t fold_pack_slices(uint32_t minCS, uint32_t maxCS, uint32_t E, uint32_t dim) {
+static std::atomic<int> g_fold_bits{-1};
+void set_fold_bits(int v) { g_fold_bits.store(v < 0 ? -1 : (v ? 1 : 0)); }
+// Like "fold_rot", "fold_pack" (else PM_FOLD_PACK, default on) and "fold_bits"
+// (else PM_FOLD_BITS, default on) are read here only, while a server's image is
+// built; its clients share the image and so the decision.  Level 0: the plain
+// image ("fold_pack" off); 1: the packed one (FOLD_ROT512P) where the DB
+// qualifies ("fold_bits" off); 2: the bit-packed one (FOLD_ROT512Q) too.
+static int fold_pack_level() {
   static const bool env = [] { const char* e = getenv("PM_FOLD_PACK"); return !e || e[0] != '0'; }();
-  const int v = g_fold_pack.load();
-  if (!(v < 0 ? env : v == 1) || fold_form(minCS, maxCS, E, true) != FOLD_ROT512) return 0;
+  static const bool envb = [] { const char* e = getenv("PM_FOLD_BITS"); return !e || e[0] != '0'; }();
+  const int v = g_fold_pack.load(), b = g_fold_bits.load();
+  if (!(v < 0 ? env : v == 1)) return 0;
+  return (b < 0 ? envb : b == 1) ? 2 : 1;
+}
+// Whole packed slices: 16 coordinate words each, inside the folded E & ~3 words.
+uint32_t fold_pack_slices(uint32_t minCS, uint32_t maxCS, uint32_t E, uint32_t dim) {
+  if (fold_pack_level() < 1 || fold_form(minCS, maxCS, E, true) != FOLD_ROT512) return 0;
   return fold_pack_shape(E, dim);
 }
+// The shape rule of the bit-packed image: a DB that takes the packed image (npk
+// != 0: FOLD_ROT512's shape, dim % 16 == 0, zero low halves), whose constant
+// bits (row_bits_or's flags) allow 12-bit coordinate fields, 20-bit id fields
+// or both, takes the fields that give the fewest slices, if those are fewer
+// than the packed image's; otherwise 0 (also where "fold_bits" is off).  Quads of four words: dim % 4 == 0 and
+// (E & ~3) % 2 == 0 hold for every such shape.
+uint32_t fold_bits_form(uint32_t E, uint32_t dim, uint32_t npk, uint32_t flags) {
+  if (fold_pack_level() < 2 || !npk || (flags & kRowLowHalf)) return 0;
+  const bool cq = !(flags & kRowCoordBits), iq = !(flags & kRowIdBits);
+  uint32_t best = 0, best_nsl = (E & ~3u) / 4 - npk;
+  auto offer = [&](uint32_t w1, uint32_t w2) {
+    const uint32_t qf = w1 | (w2 << 8) | ((dim / 4) << 16), nsl = fold_bits_nsl(fold_bits_of(qf, E));
+    if (nsl < best_nsl) { best = qf; best_nsl = nsl; }
+  };
+  if (iq) offer(16, 20);
+  if (cq) offer(12, 32);
+  if (cq && iq) offer(12, 20);
+  return best;
+}
+uint32_t fold_bits_slices(uint32_t qf, uint32_t E) { return qf ? fold_bits_nsl(fold_bits_of(qf, E)) : 0; }
 uint32_t fold_pack_shape(uint32_t E, uint32_t dim) {
   return dim && dim % 16 == 0 && dim / 8 <= E / 4 ? dim / 16 : 0;
 }
@@ -1338,26 +1545,31 @@ void answer_pack_image(hipStream_t st, uint64_t* img, const uint64_t* rows, uint
   if (grid > 256 * 32) grid = 256 * 32;
   if (grid) hipLaunchKernelGGL(k_answer_pack_image, dim3(grid), dim3(kBlock), 0, st, (uint4*)img, rows, nitems, E, nseg, dim / 8);
 }
-bool coord_low_zero(hipStream_t st, const uint64_t* rows, uint64_t nrows, uint32_t E, uint32_t dim, uint32_t* flag) {
-  if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return false;
-  unsigned grid = cdiv(nrows * (dim / 4), kBlock);
+uint32_t row_bits_or(hipStream_t st, const uint64_t* rows, uint64_t nrows, uint32_t E, uint32_t dim, uint32_t* flag) {
+  const uint32_t all = kRowLowHalf | kRowCoordBits | kRowIdBits;
+  if (hipMemsetAsync(flag, 0, 4, st) != hipSuccess) return all;
+  unsigned grid = cdiv(nrows * (E / 2), kBlock);
   if (grid > 256 * 32) grid = 256 * 32;
-  if (grid) hipLaunchKernelGGL(k_coord_low_or, dim3(grid), dim3(kBlock), 0, st, rows, nrows, E, dim, flag);
-  uint32_t h = 1;
+  if (grid) hipLaunchKernelGGL(k_row_bits_or, dim3(grid), dim3(kBlock), 0, st, rows, nrows, E, dim, flag);
+  uint32_t h = all;
   if (hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-    return false;
-  return h == 0;
+    return all;
+  return h;
 }
-uint64_t fold_image_words(uint32_t SS, uint32_t E, uint32_t CS, uint32_t npk) {
-  return (uint64_t)(E / 4 - npk) * (SS / rot_nch(CS)) * (kRotBufBytes / 8);
+uint64_t fold_image_words(uint32_t SS, uint32_t E, uint32_t CS, uint32_t npk, uint32_t qf) {
+  const uint32_t nsl = qf ? fold_bits_slices(qf, E) : E / 4 - npk;
+  return (uint64_t)nsl * (SS / rot_nch(CS)) * (kRotBufBytes / 8);
 }
 void fold_image(hipStream_t st, uint64_t* img, const uint64_t* rows, uint64_t N, uint32_t SS, uint32_t E, uint32_t CS,
-                uint32_t npk) {
-  const uint64_t nitems = fold_image_words(SS, E, CS, npk) / 2;
+                uint32_t npk, uint32_t qf) {
+  const uint64_t nitems = fold_image_words(SS, E, CS, npk, qf) / 2;
   unsigned grid = cdiv(nitems, kBlock);
   if (grid > 256 * 32) grid = 256 * 32;
-  hipLaunchKernelGGL(k_fold_image, dim3(grid), dim3(kBlock), 0, st, (uint4*)img, rows, N, SS / rot_nch(CS), E, nitems,
-                     CS, npk);
+  if (qf)   // CS 512 only (fold_bits_form)
+    hipLaunchKernelGGL(k_fold_image_bits, dim3(grid), dim3(kBlock), 0, st, (uint4*)img, rows, N, SS / rot_nch(CS), E, nitems, qf);
+  else
+    hipLaunchKernelGGL(k_fold_image, dim3(grid), dim3(kBlock), 0, st, (uint4*)img, rows, N, SS / rot_nch(CS), E, nitems,
+                       CS, npk);
 }
 void fold_image_map(uint32_t CS, uint32_t SS, uint32_t npk, uint64_t x0, uint64_t n, uint64_t* row, uint32_t* word,
                     uint8_t* packed) {
@@ -1368,10 +1580,10 @@ void fold_image_map(uint32_t CS, uint32_t SS, uint32_t npk, uint64_t x0, uint64_
 }
 int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint64_t* db, uint32_t E,
               uint32_t minCS, uint32_t maxCS, const uint64_t* zero16, uint32_t clients, bool have_img,
-               uint32_t minH, uint32_t npk) {
+               uint32_t minH, uint32_t npk, uint32_t qf) {
   // the form follows from what the engine was created with (have_img) and the
   // shape alone (fold_form): the same inputs that decided whether PmPart::tab exists
-  const int form = fold_form(minCS, maxCS, E, have_img, npk);
+  const int form = fold_form(minCS, maxCS, E, have_img, npk, qf);
   const uint32_t EX = E & ~3u;
   if (EX == 0) {
     hipLaunchKernelGGL(k_prep_fold<2>, dim3(cdiv((uint64_t)maxH * E, kBlock), np), dim3(kBlock), 0,
@@ -1387,10 +1599,12 @@ int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint
     else if (sw == 4) hipLaunchKernelGGL(k_prep_fold_blk<4>, grid, blk, lds, st, d, db, zero16, E, w0);
     else hipLaunchKernelGGL(k_prep_fold_blk<2>, grid, blk, lds, st, d, db, zero16, E, w0);
   };
-  if (form == FOLD_ROT512 || form == FOLD_ROT512P || form == FOLD_ROT1024 || form == FOLD_PIPE) {
+  if (form == FOLD_ROT512 || form == FOLD_ROT512P || form == FOLD_ROT512Q || form == FOLD_ROT1024 || form == FOLD_PIPE) {
     // (SW, G): CS 512 -> (4, 1), 1024 -> (4, 2), 2048 -> (2, 2); EX % SW == 0
     // the packed image: npk slices in place of the 2 npk coordinate slices
-    const uint32_t psw = maxCS == 2048 ? 2 : 4, nsl = EX / psw - (form == FOLD_ROT512P ? npk : 0);
+    // the bit-packed image: its own slice count
+    const uint32_t psw = maxCS == 2048 ? 2 : 4;
+    const uint32_t nsl = form == FOLD_ROT512Q ? fold_bits_slices(qf, E) : EX / psw - (form == FOLD_ROT512P ? npk : 0);
     const uint32_t K = clients && np % clients == 0 ? clients : 1, npg = (np / K) * ng;
     const uint32_t lw = 16 / psw, per_pg = K * cdiv(nsl, lw) * lw;
 #ifndef PM_FOLD_NB512
@@ -1405,13 +1619,15 @@ int prep_fold(hipStream_t st, const PmPart* d, int np, uint32_t maxH, const uint
       const uint32_t ngc = minH >= HB ? 0u : (uint32_t)cdiv(maxH, HB);
       const uint32_t nvg = ngc ? K * ngc : (uint32_t)cdiv((uint64_t)K * maxH, HB), npv = (np / K) * nvg;
       // whole tiles of GB pairs x SB slices, dealt over the 8 XCDs (the kernel's sixth parameter: the packed
-      // coordinate slices, 0 for the plain image)
-      const uint32_t grid = 8 * cdiv((uint64_t)cdiv(npv, PM_ROT_GB) * cdiv(nsl, PM_ROT_SB), 8) * PM_ROT_GB * PM_ROT_SB;
+      // coordinate slices, 0 for the plain image; its ninth: the bit-packed image's fields)
+      const uint32_t GB = form == FOLD_ROT512Q ? PM_ROTQ_GB : PM_ROT_GB, SB = form == FOLD_ROT512Q ? PM_ROTQ_SB : PM_ROT_SB;
+      const uint32_t grid = 8 * cdiv((uint64_t)cdiv(npv, GB) * cdiv(nsl, SB), 8) * GB * SB;
       if (form != FOLD_ROT1024)
         hipLaunchKernelGGL(k_prep_fold_rot<512>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv,
-                           form == FOLD_ROT512P ? npk : 0u, K, ngc);
+                           form == FOLD_ROT512P ? npk : 0u, K, ngc, form == FOLD_ROT512Q ? qf : 0u, GB, SB);
       else
-        hipLaunchKernelGGL(k_prep_fold_rot<1024>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, 0u, K, ngc);
+        hipLaunchKernelGGL(k_prep_fold_rot<1024>, dim3(grid), dim3(kFoldThreads), 0, st, d, E, nvg, nsl, npv, 0u, K, ngc,
+                           0u, GB, SB);
       return form;
     }
     const uint32_t nb = maxCS == 512 ? PM_FOLD_NB512 : 3;   // LDS buffers: <= 150 KB
